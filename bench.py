@@ -8,18 +8,26 @@ Workload = BASELINE.json configs[1]: 224x224 images, input_ids = [BOS, <image>, 
 random-init LLaMA-2-7B / ViT-L/14 shapes (no weights exist offline), bf16 compute, inputs resident in HBM.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` (dominant kernel = the bf16 MFMA
-GEMM, timed live with HIP events on its launch stream inside the timed region) and, at N=1, `cpu_baseline` (the CPU
-oracle timed on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times exactly --steps steps and prints
+the headline (`value`, `ms_per_step` = wall time of the timed steps / --steps) and nothing it needs a second measurement for.
+--full adds everything else: `roofline` (dominant kernel = the bf16 MFMA GEMM, timed live with HIP events on its launch stream inside
+the timed region, shader clock sampled by rocm-smi), at N=1 the extras (micro-batches 8 / 120 / 60 / 30, generate tokens/s, the stage-3
+LoRA leg) and `cpu_baseline` (the CPU oracle timed on a bounded sample of the same workload).
+--dump-outputs DIR writes what the last timed step computed (loss, gradient norm, a fixed seeded sample of every trainable store's
+gradient and updated master weights; --decode: the generated token ids) as DIR/<name>.npy, float32 / float64, at most 64 MB in all.
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -156,10 +164,11 @@ class _SmiSampler:
 LLAMA_LINEAR_PARAMS_PER_LAYER = 12288 * 4096 + 4096 * 4096 + 22016 * 4096 + 4096 * 11008  # qkv | o | gate,up | down
 
 
-def decode_probe(model, dev, weights="bf16", prompt_tokens=60, new_tokens=256, seed=322):
+def decode_probe(model, dev, weights="bf16", prompt_tokens=60, new_tokens=256, seed=322, keep=None):
     """BASELINE configs[4] / SURVEY §8d config 5: one 224x224 image, a 60-token prompt (S0 = 203 positions), greedy generate through the
     captured hipGraph.  `value` = new tokens / wall time of the whole generate() call (ViT + projector + prefill included, as cli_qa.py
-    runs it); the roofline leg isolates the per-token step as the difference of two run lengths."""
+    runs it); the roofline leg isolates the per-token step as the difference of two run lengths.  `keep` (a list): receives the token
+    ids of the full-length call."""
     g = torch.Generator().manual_seed(seed)
     ids = torch.randint(3, 32000, (1, prompt_tokens), generator=g)
     ids[0, 0], ids[0, 1] = 1, -200
@@ -173,6 +182,8 @@ def decode_probe(model, dev, weights="bf16", prompt_tokens=60, new_tokens=256, s
         t0 = time.perf_counter()
         out = model.generate(ids, max_new_tokens=n, **kw)
         torch.cuda.synchronize()
+        if keep is not None and n == new_tokens:
+            keep[:] = [out]
         return time.perf_counter() - t0, out.shape[1]
 
     run(4)  # graph capture, weight repacks, allocator warm-up
@@ -198,9 +209,10 @@ def decode_probe(model, dev, weights="bf16", prompt_tokens=60, new_tokens=256, s
                          "timing": f"wall clock (synchronised) of generate() at {n_short} and {new_tokens} new tokens; per-token = difference / {new_tokens - n_short}"}}
 
 
-def timed_run(engine, batch, steps, warmup, world, lib, on_timed_start=None):
-    """W untimed steps, then exactly K steps bracketed by barrier + synchronize; the GEMM launches inside the timed region are timed live
-    with HIP events on their launch stream (lhrs_gemm_profile_*), every step boundary carries an event (median step time)."""
+def timed_run(engine, batch, steps, warmup, world, lib, on_timed_start=None, profile=True):
+    """W untimed steps, then exactly K steps bracketed by barrier + synchronize; every step boundary carries an event (median step time,
+    SURVEY §8d).  profile: the GEMM launches inside the timed region are timed live with HIP events on their launch stream
+    (lhrs_gemm_profile_*: the roofline leg of --full); `prof` / `kinds` are None without it."""
     import ctypes
     from lhrs_bot_amd import _lib
 
@@ -373,8 +385,9 @@ def timed_run(engine, batch, steps, warmup, world, lib, on_timed_start=None):
     for r in getattr(engine, "reducers", {}).values():   # N > 1: time the compute stream spends waiting for the gradient collectives
         r.measure = True
         r.blocked_ms()
-    lib.lhrs_gemm_profile_stride(PROFILE_STRIDE)
-    _lib.check(lib.lhrs_gemm_profile_enable(int(os.environ.get("LHRS_GEMM_PROFILE_SAMPLES", "16000"))), "gemm_profile_enable")   # 0: A/B of the event overhead
+    if profile:
+        lib.lhrs_gemm_profile_stride(PROFILE_STRIDE)
+        _lib.check(lib.lhrs_gemm_profile_enable(int(os.environ.get("LHRS_GEMM_PROFILE_SAMPLES", "16000"))), "gemm_profile_enable")   # 0: A/B of the event overhead
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -390,18 +403,60 @@ def timed_run(engine, batch, steps, warmup, world, lib, on_timed_start=None):
         torch.distributed.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    prof = (ctypes.c_double * 5)()
-    _lib.check(lib.lhrs_gemm_profile_read(ctypes.addressof(prof)), "gemm_profile_read")
-    kinds = (ctypes.c_double * 30)()
-    _lib.check(lib.lhrs_gemm_profile_read_kinds(ctypes.addressof(kinds)), "gemm_profile_read_kinds")
-    lib.lhrs_gemm_profile_enable(0)
+    prof = kinds = None
+    if profile:
+        prof = (ctypes.c_double * 5)()
+        _lib.check(lib.lhrs_gemm_profile_read(ctypes.addressof(prof)), "gemm_profile_read")
+        kinds = (ctypes.c_double * 30)()
+        _lib.check(lib.lhrs_gemm_profile_read_kinds(ctypes.addressof(kinds)), "gemm_profile_read_kinds")
+        lib.lhrs_gemm_profile_enable(0)
+        prof, kinds = list(prof), list(kinds)
     blocked = 0.0
     for r in getattr(engine, "reducers", {}).values():
         blocked += r.blocked_ms()[1]
         r.measure = False
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
     median = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
-    return dict(dt=dt, loss=loss, prof=list(prof), kinds=list(kinds), median_ms=median, blocked_ms_per_step=blocked / max(1, steps))
+    return dict(dt=dt, loss=loss, prof=prof, kinds=kinds, median_ms=median, blocked_ms_per_step=blocked / max(1, steps))
+
+
+DUMP_SAMPLE = 1 << 21          # elements kept of a larger output array (8 MB of float32): a fixed, seeded sample
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs writes at most this much in all
+
+
+def dump_sample(t, k=DUMP_SAMPLE, seed=0):
+    """`t` flattened, whole if it has at most k elements, else at k sorted positions drawn with a fixed seed (the same positions for the
+    same numel, so that two builds' dumps compare element for element); float64 stays float64, everything else becomes float32."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > k:
+        idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), k))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.to(torch.float64 if flat.dtype == torch.float64 else torch.float32).cpu().numpy()
+
+
+def train_step_outputs(engine, loss):
+    """What a caller of one training step receives from it: the loss, the gradient norm it clipped with, and every trainable store's
+    gradient and updated master weights (sampled by dump_sample)."""
+    out = {"loss": np.asarray(float(loss.item()), dtype=np.float64)}
+    if engine.max_grad_norm > 0:
+        out["grad_norm"] = np.asarray(engine.grad_norm(), dtype=np.float64)
+    for st in engine.stores:
+        out[f"{st.name}_grad"] = dump_sample(st.grad)
+        out[f"{st.name}_master"] = dump_sample(st.master)
+    return out
+
+
+def write_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays: name -> float32 / float64 numpy array, written as dirname/<name>.npy."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {limit}-byte limit")
+    bad = [n for n, a in arrays.items() if a.dtype not in (np.float32, np.float64)]
+    if bad:
+        raise SystemExit(f"--dump-outputs: {bad} are not float32 / float64")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 # every 7th launch of each GEMM variant is bracketed by HIP events: timing every launch costs 1.0 % (micro-batch 30) / 2.2 % (micro-batch 8) of
@@ -476,7 +531,7 @@ def roofline_block(prof, kinds, steps, B, S, scale_layers, sclk=None, watts=None
 
 
 def spawn_ranks(n: int):
-    """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU, as the reference's
+    """`python bench.py --gpus N` without a launcher: run torch.distributed.run as a child process, one rank per GPU, as the reference's
     `deepspeed --num_gpus=8` does (Script/train_stage1.sh:6-17).  Rank 0 prints the JSON line; the exit status is the launcher's."""
     import socket
     with socket.socket() as sk:
@@ -486,7 +541,8 @@ def spawn_ranks(n: int):
                OMP_NUM_THREADS=os.environ.get("OMP_NUM_THREADS", "8"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", port, os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(sys.executable, cmd, env)
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)   # killed by a signal: the shell's 128 + signal number
 
 
 def main():
@@ -497,13 +553,18 @@ def main():
     ap.add_argument("--micro-batch", type=int, default=240,
                     help="samples per GPU per step.  240 since the end of round 6: 195 GB of saved activations, 245 GB of the 288 GB allocated at the peak "
                          "(config.peak_hbm_allocated_gb) - the memory is there to be used, and every doubling halves the launch boundaries per sample and keeps the tile walks and "
-                         "the attention kernels' workgroups on whole rounds of the 256 CUs (M = 65520 = 256 tile rows; 7680 workgroups = 30 rounds): same-box 60 -> 120 +1.2 %, "
-                         "120 -> 240 +0.8 %.  Rounds 1-4 quoted 30, rounds 5-6 60 - reported next to the headline as config.micro_batch_120 / _60 / _30; the reference script uses 8 "
+                         "the attention kernels' workgroups on whole rounds of the 256 CUs (M = 65520 = 256 tile rows; 7680 workgroups = 30 rounds): same-box 60 -> 120 +1.2 %%, "
+                         "120 -> 240 +0.8 %%.  Rounds 1-4 quoted 30, rounds 5-6 60 - reported next to the headline as config.micro_batch_120 / _60 / _30; the reference script uses 8 "
                          "on 80 GB parts (Script/train_stage1.sh:11), reported as micro_batch_8 (DESIGN.md §4)")
     ap.add_argument("--caption-tokens", type=int, default=128)
     ap.add_argument("--llama-layers", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the untimed extras (micro-batch-8 step rate, generate tokens/s) after the headline run")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: roofline (live GEMM timing + clock sampling in the timed region), and at N=1 the extras and "
+                         "cpu_baseline.  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the untimed extras (micro-batch-8 step rate, generate tokens/s) after the headline run")
     ap.add_argument("--decode", action="store_true",
                     help="make BASELINE configs[4] the line: cli_qa-shaped greedy generate (1 image, 60-token prompt), tokens/s with an HBM roofline")
     ap.add_argument("--new-tokens", type=int, default=256, help="--decode: tokens generated per step")
@@ -518,6 +579,8 @@ def main():
     ap.add_argument("--bits", type=int, default=16, choices=[16, 8],
                     help="stages 2/3 only: 8 = frozen decoder linears in e4m3 (the reference's `bits: 8` base weights)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(a.gpus)  # does not return
@@ -562,10 +625,12 @@ def main():
     if a.decode:
         if world > 1:
             raise SystemExit("--decode is a single-sequence latency run (BASELINE configs[4]: 1xMI355X): replicas only, run it with --gpus 1")
-        res = None
+        res, tokens = None, []
         for _ in range(max(1, a.steps)):  # a "step" = one whole generate() call; the best of them is reported
-            r = decode_probe(model, dev, a.weights, new_tokens=a.new_tokens)
+            r = decode_probe(model, dev, a.weights, new_tokens=a.new_tokens, keep=tokens)
             res = r if res is None or r["value"] > res["value"] else res
+        if a.dump_outputs:
+            write_outputs(a.dump_outputs, {"tokens": tokens[0].cpu().numpy().astype(np.float64)})   # token ids of the last generate() call
         res.update({"n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * res["new_tokens"] / res["value"], 3),
                     "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if a.weights == "bf16" else "e4m3 weights, bf16 activations",
                     "data": "synthetic", "config": {"workload": "BASELINE configs[4]: cli_qa.py single-image VQA generate, hipGraph-captured decode, "
@@ -588,8 +653,8 @@ def main():
                             comm_dtype=getattr(torch, a.comm_dtype))
     batch = make_batch(B, T, dev, seed=322 + rank)  # reference seed convention (main_pretrain_stage1.py:281-287)
 
-    smi = _SmiSampler() if rank == 0 and os.environ.get("LHRS_BENCH_NO_SMI") != "1" else None   # LHRS_BENCH_NO_SMI=1: A/B of the sampler's own cost
-    run = timed_run(engine, batch, a.steps, a.warmup, world, lib, on_timed_start=smi.start if smi is not None else None)
+    smi = _SmiSampler() if a.full and rank == 0 and os.environ.get("LHRS_BENCH_NO_SMI") != "1" else None   # LHRS_BENCH_NO_SMI=1: A/B of the sampler's own cost
+    run = timed_run(engine, batch, a.steps, a.warmup, world, lib, on_timed_start=smi.start if smi is not None else None, profile=a.full)
     sclk, watts = smi.stop() if smi is not None else (None, None)
     dt, loss, prof, kinds = run["dt"], run["loss"], run["prof"], run["kinds"]
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -597,6 +662,8 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax.item())
     final_loss = float(loss.item())
+    if a.dump_outputs and rank == 0:   # before the extras of --full, which run other batches through the same engine
+        write_outputs(a.dump_outputs, train_step_outputs(engine, loss))
     peak_gb = torch.cuda.max_memory_allocated(dev) / 1e9   # of the headline run (model + saved activations of one step), before the extras
     dp = None
     if getattr(engine, "_finite_trace", None):
@@ -665,10 +732,11 @@ def main():
             "loss": round(final_loss, 4),
             "step_mfma_frac": round(sps / world * f_alg(S) / (PEAK_BF16_TFLOPS * 1e12), 4) if scale_layers == 1.0 and a.stage == 1 else None,
             "step_mfma_frac_executed": round(sps / world * f_exec / (PEAK_BF16_TFLOPS * 1e12), 4) if scale_layers == 1.0 and a.stage == 1 else None,
-            "roofline": roofline_block(prof, kinds, a.steps, B, S, scale_layers, sclk, watts),
         }
+        if a.full:
+            res["roofline"] = roofline_block(prof, kinds, a.steps, B, S, scale_layers, sclk, watts)
         res["config"]["step_mfma_frac_executed"] = res["step_mfma_frac_executed"]   # hardware utilisation of the whole step (F_alg minus the rows the engine skips)
-        if world == 1 and not a.no_extra and a.stage == 1:
+        if a.full and world == 1 and not a.no_extra and a.stage == 1:
             extra = {}
             try:  # the reference script's micro-batch (Script/train_stage1.sh:11), same engine, its own timed region
                 if B != 8:
@@ -727,7 +795,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 extra["stage3_error"] = f"{type(e).__name__}: {e}"
             res["extra"] = extra
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(S, a.llama_layers)
             except Exception as e:  # the checker must never take the product number down with it

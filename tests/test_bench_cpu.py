@@ -1,5 +1,5 @@
-"""Host-side pieces of bench.py that need no GPU: which committed PMC pass the roofline's `traffic` is quoted from, the F_alg formula of SURVEY §8(d), and the
-argument defaults the driver relies on (N = 1, a K / W that finish within minutes)."""
+"""Host-side pieces of bench.py that need no GPU: which committed PMC pass the roofline's `traffic` is quoted from, the F_alg formula of SURVEY §8(d), the
+argument defaults the driver relies on (N = 1, a K / W that finish within minutes, a plain run), and the --dump-outputs writer."""
 import json
 import os
 import sys
@@ -41,3 +41,32 @@ def test_defaults_are_one_gpu_and_a_short_run(monkeypatch):
     except SystemExit:
         pass
     assert seen["gpus"] == 1 and seen["steps"] <= 20 and seen["warmup"] <= 5 and seen["micro_batch"] == 240 and seen["stage"] == 1 and seen["llama_layers"] == 32
+    assert seen["full"] is False and seen["dump_outputs"] is None      # a plain run measures the headline only and writes nothing
+
+
+def test_dump_sample_is_whole_or_a_fixed_seeded_sample():
+    import numpy as np
+    import torch
+    small = torch.arange(10, dtype=torch.bfloat16)
+    got = bench.dump_sample(small)
+    assert got.dtype == np.float32 and np.array_equal(got, np.arange(10, dtype=np.float32))
+    assert bench.dump_sample(torch.ones(3, dtype=torch.float64)).dtype == np.float64
+    big = torch.randn(5000, 7)
+    a, b = bench.dump_sample(big, k=1000), bench.dump_sample(big.clone(), k=1000)
+    assert a.dtype == np.float32 and 900 < a.size <= 1000 and np.array_equal(a, b)     # same positions for the same numel
+    assert np.isin(a, big.numpy().reshape(-1)).all()
+
+
+def test_write_outputs_writes_float_npy_within_the_limit(tmp_path):
+    import numpy as np
+    import pytest
+    arrays = {"loss": np.asarray(2.5, dtype=np.float64), "w": np.arange(6, dtype=np.float32)}
+    bench.write_outputs(str(tmp_path / "d"), arrays)
+    assert sorted(os.listdir(tmp_path / "d")) == ["loss.npy", "w.npy"]
+    assert float(np.load(tmp_path / "d" / "loss.npy")) == 2.5 and np.array_equal(np.load(tmp_path / "d" / "w.npy"), arrays["w"])
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "e"), {"w": np.zeros(1 << 20, dtype=np.float32)}, limit=1 << 20)
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "e"), {"ids": np.arange(3)})
+    assert not os.path.exists(tmp_path / "e")
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20 and 2 * 2 * 4 * bench.DUMP_SAMPLE + 16 <= bench.DUMP_LIMIT_BYTES   # two stores' gradient + master

@@ -1,4 +1,4 @@
-"""bench.py contract: one JSON line with the driver's keys, the roofline and cpu_baseline objects (tiny model so that it runs in seconds)."""
+"""bench.py contract: one JSON line with the driver's keys; with --full the roofline and cpu_baseline objects (tiny model so that it runs in seconds)."""
 import json
 import os
 import subprocess
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.timeout(900)
 def test_bench_emits_the_contract_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--llama-layers", "2",
-                          "--micro-batch", "15"], capture_output=True, text=True, timeout=800, cwd=ROOT)
+                          "--micro-batch", "15", "--full"], capture_output=True, text=True, timeout=800, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -57,6 +57,31 @@ def test_bench_emits_the_contract_line():
     s3 = e["stage3_lora_r8_b32"]
     assert s3["value"] > 0 and s3["micro_batch_per_gpu"] == 32 and s3["steps"] == 8 and 0 < s3["dominant_kernel_frac"] < 1 and s3["variants"]
     assert d["config"]["stage3_lora_r8_b32"]["value"] == s3["value"]
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_line_times_only_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full): the headline keys, exactly --steps timed steps, none of the --full measurements; --dump-outputs writes the
+    last timed step's loss, gradient norm and the sampled projector gradient / master weights as float32 / float64 .npy, at most 64 MB."""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--llama-layers", "2",
+                          "--micro-batch", "4", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=500, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "loss"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "samples/s" and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]            # samples/s and ms_per_step describe the same timed steps
+    for k in ("roofline", "cpu_baseline", "extra", "micro_batch_8"):
+        assert k not in d, k
+    files = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert set(files) == {"loss", "grad_norm", "rgb_pooler_grad", "rgb_pooler_master"}, sorted(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(os.path.getsize(tmp_path / "out" / f"{n}.npy") for n in files) <= 64 << 20
+    assert abs(float(files["loss"]) - d["loss"]) < 1e-3 and float(files["grad_norm"]) > 0
+    assert all(np.isfinite(a).all() for a in files.values()) and files["rgb_pooler_master"].size == files["rgb_pooler_grad"].size > 0
 
 
 @pytest.mark.timeout(900)
