@@ -602,7 +602,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_res_kernel(AttnArgs a) {
 #pragma unroll
     for (int i = 0; i < DB; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     int kv_end = kv_len;
-    if (CAUSAL) kv_end = max(0, min(kv_len, g * 16 + 16 + coff));
+    // the last key any STORED row of the group sees: a partial last group (rows past q_len) must not reach past the kv_need rows loaded above -
+    // with causal_off > 0 that can be another 64-key tile, whose LDS rows hold whatever the previous workgroup left there (NaN * 0 = NaN)
+    if (CAUSAL) kv_end = max(0, min(kv_len, min(g * 16 + 16, q_len) + coff));
     const int ntiles = (kv_end + 63) >> 6;
     for (int j = 0; j < ntiles; ++j) {
       const char* kt = lds_k + j * TILE;
@@ -745,7 +747,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_res_kernel(AttnArgs a) {
 #pragma unroll
     for (int i = 0; i < DB; ++i) dq[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     int kv_end = kv_len;
-    if (CAUSAL) kv_end = max(0, min(kv_len, g * 16 + 16 + coff));
+    if (CAUSAL) kv_end = max(0, min(kv_len, min(g * 16 + 16, q_len) + coff));  // within the kv_need rows loaded (forward kernel)
     const int ntiles = (kv_end + 63) >> 6;
     for (int j = 0; j < ntiles; ++j) {
       const char* kt = lds_k + j * TILE;

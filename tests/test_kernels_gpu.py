@@ -438,14 +438,24 @@ def ref_attention(q, k, v, causal, kv_len, scale):
 
 
 def run_attention_case(D, H, seqs, causal, same_qkv_buffer):
-    """seqs: list of (Lq, Lkv, kv_len_valid)."""
+    """seqs: list of (Lq, Lkv, kv_len_valid).  same_qkv_buffer: the product's layout - q / k / v (and dq / dk / dv) are column slices of one
+    packed [T, 3*H*D] buffer (row stride 3*H*D, text.py), or with Lq != Lkv q on its own and k / v slices of one [T, 2*H*D] buffer (the pooler)."""
     g = torch.Generator().manual_seed(D + H + len(seqs))
     tq = sum(s[0] for s in seqs)
     tk = sum(s[1] for s in seqs)
     scale = 1.0 / math.sqrt(D)
-    q = bf(torch.randn(tq, H * D, generator=g)).to(DEV)
-    k = bf(torch.randn(tk, H * D, generator=g)).to(DEV)
-    v = bf(torch.randn(tk, H * D, generator=g)).to(DEV)
+    HD = H * D
+    if same_qkv_buffer and tq == tk:
+        qkv = bf(torch.randn(tq, 3 * HD, generator=g)).to(DEV)
+        q, k, v = qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:]
+    elif same_qkv_buffer:
+        q = bf(torch.randn(tq, HD, generator=g)).to(DEV)
+        kv = bf(torch.randn(tk, 2 * HD, generator=g)).to(DEV)
+        k, v = kv[:, :HD], kv[:, HD:]
+    else:
+        q = bf(torch.randn(tq, H * D, generator=g)).to(DEV)
+        k = bf(torch.randn(tk, H * D, generator=g)).to(DEV)
+        v = bf(torch.randn(tk, H * D, generator=g)).to(DEV)
     do = bf(torch.randn(tq, H * D, generator=g)).to(DEV)
     entries, qo, ko = [], 0, 0
     for (lq, lk, kvl) in seqs:
@@ -467,9 +477,17 @@ def run_attention_case(D, H, seqs, causal, same_qkv_buffer):
     # backward
     delta = torch.zeros(nseq, H, LTq, device=DEV, dtype=torch.float32)
     hk.attn_delta(o, do, delta, desc, nseq, H, D, max_q, LTq)
-    dq = torch.full_like(q, float("nan"))
-    dk = torch.full_like(k, float("nan"))
-    dv = torch.full_like(v, float("nan"))
+    if same_qkv_buffer and tq == tk:
+        dqkv = torch.full((tq, 3 * HD), float("nan"), device=DEV, dtype=torch.bfloat16)
+        dq, dk, dv = dqkv[:, :HD], dqkv[:, HD:2 * HD], dqkv[:, 2 * HD:]
+    elif same_qkv_buffer:
+        dq = torch.full((tq, HD), float("nan"), device=DEV, dtype=torch.bfloat16)
+        dkv = torch.full((tk, 2 * HD), float("nan"), device=DEV, dtype=torch.bfloat16)
+        dk, dv = dkv[:, :HD], dkv[:, HD:]
+    else:
+        dq = torch.full_like(q, float("nan"))
+        dk = torch.full_like(k, float("nan"))
+        dv = torch.full_like(v, float("nan"))
     hk.attn_bwd(q, k, v, do, lse, delta, dq, dk, dv, desc, nseq, H, D, max_q, max_kv, LTq, causal, scale)
     torch.cuda.synchronize()
     qo = ko = 0
@@ -491,19 +509,19 @@ def run_attention_case(D, H, seqs, causal, same_qkv_buffer):
 
 
 def test_attention_vit_shape():
-    run_attention_case(64, 16, [(257, 257, 257)] * 2, causal=False, same_qkv_buffer=False)
+    run_attention_case(64, 16, [(257, 257, 257)] * 2, causal=False, same_qkv_buffer=True)
 
 
 def test_attention_pooler_groups():
-    run_attention_case(64, 16, [(64, 320, 320), (48, 304, 304), (32, 288, 288)] * 2, causal=False, same_qkv_buffer=False)
+    run_attention_case(64, 16, [(64, 320, 320), (48, 304, 304), (32, 288, 288)] * 2, causal=False, same_qkv_buffer=True)
 
 
 def test_attention_llama_causal():
-    run_attention_case(128, 32, [(273, 273, 273), (273, 273, 250)], causal=True, same_qkv_buffer=False)
+    run_attention_case(128, 32, [(273, 273, 273), (273, 273, 250)], causal=True, same_qkv_buffer=True)
 
 
 def test_attention_long_sequences_use_tiled_kernels():
-    run_attention_case(128, 2, [(700, 700, 650), (330, 330, 330)], causal=True, same_qkv_buffer=False)
+    run_attention_case(128, 2, [(700, 700, 650), (330, 330, 330)], causal=True, same_qkv_buffer=True)
     run_attention_case(64, 4, [(100, 900, 900)], causal=False, same_qkv_buffer=False)
 
 
