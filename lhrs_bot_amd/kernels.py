@@ -75,20 +75,24 @@ GEMM_KIND_NAMES = ("gemm_nt_256s_kernel plain", "gemm_nt_256s_kernel SwiGLU-fwd"
 
 class gemm_kernel_census:
     """with gemm_kernel_census() as c: ...  -> c.counts = {kernel instantiation: timed launches} of the persistent GEMM kernels that ran inside the block (the library's live
-    profile counters, include/lhrs_hip.h: lhrs_gemm_profile_*): which kernel the shape rules gave each product - the parity tests record it next to their numbers."""
+    profile counters, include/lhrs_hip.h: lhrs_gemm_profile_*): which kernel the shape rules gave each product - the parity tests record it next to their numbers.
+    c.launches = every GEMM launch inside the block, timed or not (lhrs_gemm_profile_read out[3]: small tiles, split-K tails and e4m3 kernels included)."""
 
     def __enter__(self):
         _lib.check(_L().lhrs_gemm_profile_stride(1), "gemm_profile_stride")
         _lib.check(_L().lhrs_gemm_profile_enable(20000), "gemm_profile_enable")
-        self.counts = {}
+        self.counts, self.launches = {}, 0
         return self
 
     def __exit__(self, *exc):
         kinds = (ctypes.c_double * 30)()
+        totals = (ctypes.c_double * 5)()
         torch.cuda.synchronize()
         _lib.check(_L().lhrs_gemm_profile_read_kinds(ctypes.addressof(kinds)), "gemm_profile_read_kinds")
+        _lib.check(_L().lhrs_gemm_profile_read(ctypes.addressof(totals)), "gemm_profile_read")
         _L().lhrs_gemm_profile_enable(0)
         self.counts = {GEMM_KIND_NAMES[k]: int(kinds[3 * k]) for k in range(10) if kinds[3 * k] > 0}
+        self.launches = int(totals[3])
         return False
 
 
