@@ -45,6 +45,11 @@ def parse_option(args=None):
     p.add_argument("--tokenizer-path", type=str, default=None, help="directory holding the LLaMA-2 tokenizer files")
     p.add_argument("--synthetic-prompt", type=int, default=0, metavar="T", help="non-interactive: T random prompt ids, greedy decode, JSON line")
     p.add_argument("--llama-layers", type=int, default=32)
+    p.add_argument("--sampler", default="torch", choices=["torch", "device"],
+                   help="who draws the token: HF-style torch warpers + multinomial, or the one-launch HIP sampler (lhrs_sample_rows).  "
+                        "device: every turn draws from the Philox stream of --seed starting at step 0, so the same conversation replays to the "
+                        "same answers (torch: one global generator runs on across the turns)")
+    p.add_argument("--repetition-penalty", type=float, default=1.0, help="HF repetition_penalty over the generated tokens (the web UI uses 1.05)")
     cfg = ConfigDict(p.parse_args(wandb=True, args=args))
     opts = cfg.get("opts") or []
     if len(opts) % 2:
@@ -149,7 +154,8 @@ def main(config):
         stopping_criteria = KeywordsStoppingCriteria([stop_str], tokenizer, input_ids)
         with torch.inference_mode():
             output_ids = model.generate(input_ids, images=image_tensor, do_sample=True, max_new_tokens=int(config.max_new_tokens), temperature=0.4,
-                                        streamer=_Streamer(tokenizer), use_cache=True, stopping_criteria=[stopping_criteria], weights=weights)
+                                        streamer=_Streamer(tokenizer), use_cache=True, stopping_criteria=[stopping_criteria], weights=weights,
+                                        sampler=config.sampler, repetition_penalty=float(config.repetition_penalty), seed=int(config.seed))
         outputs = tokenizer.decode(output_ids[0]).strip().split("<s>")[-1].strip()
         conv.messages[-1][-1] = outputs
         if config.debug:

@@ -301,6 +301,20 @@ int lhrs_gather_rows(const void* src, long ld_src, const int* idx, void* dst, lo
 int lhrs_scatter_rows(const void* src, long ld_src, const int* idx, void* dst, long ld_dst, int n, int dim, void* stream);
 /* greedy decoding pick (HF GenerationMixin argmax, do_sample=False: main_vqa.py:205-214, cli_qa.py:176-186) */
 int lhrs_argmax_rows(const float* x, long ld, long* out, int n, int V, void* stream);
+/* sampled decoding pick (HF generate do_sample=True: RepetitionPenaltyLogitsProcessor -> TemperatureLogitsWarper -> TopKLogitsWarper ->
+ * TopPLogitsWarper -> one draw; text_modal.py generate, cli_qa.py temperature 0.4, the web UI's top_p / repetition_penalty), one launch, one
+ * workgroup per row, V <= 32768.  x = penalised logit (seen tokens: x < 0 ? x * pen : x / pen); z = x / temperature (IEEE); top-k keeps
+ * z >= the k-th largest (ties kept); q = rint(exp(z - zmax) * 2^40) as an integer; top-p keeps a token iff the kept tokens with strictly larger z
+ * hold less than top_p of sum q; the draw is Philox4x32-10, counter (step, row, 0, 0), key (seed low, seed high), step = step_host +
+ * (step_dev ? *step_dev : 0) mod 2^32, R = ((out0 | out1 << 32) * W) >> 64 with W = sum of the surviving q, token = first index whose inclusive
+ * prefix sum of surviving q exceeds R.  The token's bit is set in `seen` when given.  mode 1 returns the first maximum of the penalised row
+ * (penalty 1: bit-identical to lhrs_argmax_rows).  weights_out (tests): q of the survivors, -1 for removed tokens; not written in mode 1. */
+int lhrs_sample_rows(const float* logits, long ld, long* out, int n, int V,
+                     int mode,                 /* 0 = draw, 1 = first maximum (greedy on the penalised logits) */
+                     float temperature, int top_k /* <=0 or >=V: off */, float top_p /* >=1: off */,
+                     float repetition_penalty /* 1: off */, unsigned* seen /* [n][(V+31)/32] bitmap, may be NULL iff penalty == 1 */,
+                     unsigned long long seed, const int* step_dev /* may be NULL */, long step_host,
+                     long long* weights_out /* [n][V], tests only, NULL in the product */, void* stream);
 int lhrs_cross_entropy(const void* logits, long ld, const int* target, float* row_loss, float* loss_out, void* dlogits,
                        long ld_d, int n, int V, void* stream);
 

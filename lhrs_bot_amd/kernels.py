@@ -695,6 +695,33 @@ def argmax_rows(logits_f32, out=None):
     return out
 
 
+def sample_rows(logits_f32, out=None, *, mode=0, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seen=None, seed=0,
+                step_dev=None, step_host=0, weights_out=None):
+    """lhrs_sample_rows: HF's repetition penalty -> temperature -> top-k -> top-p -> one Philox draw per row of fp32 logits [n, V], in one launch
+    (mode 1: first maximum of the penalised row).  `seen` [n, (V+31)//32] int32 bitmap (read for the penalty, the picked token's bit is set);
+    `step_dev` a 1-element int32 device tensor added to `step_host` (the draw's counter); `weights_out` [n, V] int64, tests only.
+    top_k None / 0 and top_p None / >= 1 switch the filter off."""
+    n, V = logits_f32.shape
+    _req(logits_f32, torch.float32, "logits")
+    assert logits_f32.stride(1) == 1
+    out = torch.empty(n, device=logits_f32.device, dtype=torch.int64) if out is None else out
+    _req(out, torch.int64, "out")
+    if seen is not None:
+        _req(seen, torch.int32, "seen")
+        assert seen.is_contiguous() and tuple(seen.shape) == (n, (V + 31) // 32), f"seen {tuple(seen.shape)} for n={n} V={V}"
+    if step_dev is not None:
+        _req(step_dev, torch.int32, "step_dev")
+    if weights_out is not None:
+        _req(weights_out, torch.int64, "weights_out")
+        assert weights_out.is_contiguous() and tuple(weights_out.shape) == (n, V)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    st = _L().lhrs_sample_rows(logits_f32.data_ptr(), logits_f32.stride(0), out.data_ptr(), n, V, int(mode), float(temperature),
+                               int(top_k or 0), 1.0 if top_p is None else float(top_p), float(repetition_penalty), _p(seen),
+                               seed - (1 << 64) if seed >= (1 << 63) else seed, _p(step_dev), int(step_host), _p(weights_out), _stream())
+    _lib.check(st, "sample_rows")
+    return out
+
+
 def cross_entropy(logits, target, want_grad=True, inplace=True):
     n, V = logits.shape
     row_loss = torch.empty(n, device=logits.device, dtype=torch.float32)

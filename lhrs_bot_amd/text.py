@@ -950,7 +950,7 @@ class TextModal:
     @torch.no_grad()
     def generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p="default",
                  top_k="default", max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id="default",
-                 return_logits=False, use_graph=True, weights="bf16", **_kw):
+                 return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, **_kw):
         """See `_generate`.  Two things happen here first: (1) `eos_token_id` defaults to the tokenizer's EOS, as HF `generate` stops on
         the generation config's EOS (pass None to disable); (2) if LoRA adapters are attached and not merged, the call runs on merged
         COPIES of the affected weights (`_lora_merged_layers`) and the base weights come back untouched."""
@@ -964,7 +964,8 @@ class TextModal:
             top_p = 0.9 if do_sample else None
         kw = dict(image_embedding=image_embedding, attention_mask=attention_mask, do_sample=do_sample, temperature=temperature, top_p=top_p,
                   top_k=top_k, max_new_tokens=max_new_tokens, use_cache=use_cache, stopping_criteria=stopping_criteria, streamer=streamer,
-                  eos_token_id=eos_token_id, return_logits=return_logits, use_graph=use_graph, weights=weights)
+                  eos_token_id=eos_token_id, return_logits=return_logits, use_graph=use_graph, weights=weights, sampler=sampler, seed=seed,
+                  repetition_penalty=repetition_penalty)
         if self.lora is None:
             return self._generate(input_ids, **kw)
         base_layers, base8, base_i8 = self.p["layers"], self.base8, self.base_int8
@@ -976,13 +977,26 @@ class TextModal:
 
     def _generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p=None,
                   top_k=None, max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id=None,
-                  return_logits=False, use_graph=True, weights="bf16", **_kw):
+                  return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, **_kw):
         """TextModal.generate (text_modal.py:528-627): prefill over the spliced embeddings, then one token at a time with
         a KV cache; returns only the NEW token ids [B, n_new] (HF generate started from inputs_embeds).  Greedy
         (do_sample=False, the evaluation scripts' mode) runs entirely in HIP kernels; with do_sample=True the HIP-computed
         fp32 logits go through HF's temperature / top-k / top-p warpers and one multinomial draw per token.  The
         single-token step is a captured hipGraph over static buffers (batch <= 16; from batch 2 the weight stream runs on MFMA); without eos / stopping criteria / streamer
-        the host never synchronises inside the loop."""
+        the host never synchronises inside the loop.
+
+        sampler="device" (with do_sample=True) replaces the torch warpers and `torch.multinomial` by ONE launch of `hk.sample_rows` per token,
+        between the graph replay and `decode_emit`: same distribution as HF, drawn by Philox from (`seed`, step, row) - `seed=None` takes
+        `torch.initial_seed()`, so `torch.manual_seed` still pins a run.  `repetition_penalty != 1` (HF RepetitionPenaltyLogitsProcessor over the
+        tokens generated so far in this call) exists in that kernel only, so it routes every pick through it whatever `sampler` says:
+        mode 0 when sampling, mode 1 (first maximum of the penalised logits) when greedy.  "One launch and nothing else" holds without an
+        EOS: with `eos_token_id` set the pad replacement of finished rows (`torch.where` + `copy_`) and the host's check still run between the
+        pick and `decode_emit`, as they do for greedy; the kernel has then already set the drawn token's bit in the seen bitmap of a finished
+        row, which nothing reads any more."""
+        if sampler not in ("torch", "device"):
+            raise ValueError(f"sampler={sampler!r}: expected 'torch' or 'device'")
+        pen = float(repetition_penalty)
+        device_pick = (sampler == "device" and do_sample) or pen != 1.0
         if streamer is not None and getattr(streamer, "skip_prompt", False):
             streamer.put(input_ids.cpu())  # transformers.TextStreamer protocol: the first put() is the prompt, which skip_prompt drops
         embeds, _, mask, _ = self.prepare_inputs_for_multimodal(input_ids, attention_mask, None, image_embedding)
@@ -1001,7 +1015,23 @@ class TextModal:
         caches = [(torch.empty((B * max_ctx, d), device=dev, dtype=torch.bfloat16), torch.empty((B * max_ctx, d), device=dev, dtype=torch.bfloat16))
                   for _ in range(len(self.p["layers"]))]
 
+        s, seen, step_dev = None, None, None
+        if device_pick:
+            seed = int(torch.initial_seed() if seed is None else seed)
+            if pen != 1.0:  # bitmap of the tokens generated so far in this call (HF started from inputs_embeds: the prompt is not in it)
+                seen = torch.zeros((B, (self.vocab + 31) // 32), device=dev, dtype=torch.int32)
+            if B <= 16:  # the draw's step counter is the session's count of emitted tokens, on the device
+                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask)
+                s.state[0], s.state[1] = S0, 0
+                step_dev = s.state[1:2]
+
+        def pick_device(logits, out=None, step_host=0):
+            return hk.sample_rows(logits, out, mode=0 if do_sample else 1, temperature=temperature, top_k=top_k, top_p=top_p,
+                                  repetition_penalty=pen, seen=seen, seed=seed, step_dev=step_dev, step_host=step_host)
+
         def pick(logits):
+            if device_pick:
+                return pick_device(logits, None if s is None else s.next_ids, 0 if s is not None else n_done)
             if not do_sample:
                 return hk.argmax_rows(logits)
             return torch.multinomial(torch.softmax(warp_logits(logits, temperature, top_k, top_p), -1), 1).squeeze(1)
@@ -1014,6 +1044,7 @@ class TextModal:
         hn = hk.rmsnorm_fwd(x.view(B, S0, d)[:, -1].contiguous(), self.p["norm_w"], self.eps)
         logits = hk.gemm_nt(hn, self.p["lm_head"], out_f32=True)  # [B, V] fp32 (HF: logits.float())
         all_logits = [logits.clone()] if return_logits else []
+        n_done = 0
         nxt = pick(logits)
 
         host_checks = eos_token_id is not None or stopping_criteria is not None or streamer is not None
@@ -1031,12 +1062,14 @@ class TextModal:
 
         n_done = 1
         if B <= 16:
-            s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask)
-            s.state[0], s.state[1] = S0, 0
+            if s is None:
+                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask)
+                s.state[0], s.state[1] = S0, 0
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                s.next_ids.copy_(nxt)
+                if nxt is not s.next_ids:
+                    s.next_ids.copy_(nxt)
                 hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, B, max_new_tokens)
                 stop = host_checks and host_step(s.out_ids[:, :1], logits)
                 while not stop and n_done < max_new_tokens:
@@ -1053,7 +1086,9 @@ class TextModal:
                         s.enqueue()
                     if return_logits:
                         all_logits.append(s.logits.clone())
-                    if do_sample:
+                    if device_pick:
+                        pick_device(s.logits, s.next_ids)
+                    elif do_sample:
                         s.next_ids.copy_(pick(s.logits))
                     else:
                         hk.argmax_rows(s.logits, out=s.next_ids)

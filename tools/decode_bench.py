@@ -1,19 +1,52 @@
-"""Decode throughput of generate() (BASELINE configs[4] shape: 1 image, short prompt, greedy, bf16 weights)."""
-import os, sys, time
+"""Decode throughput of generate() (BASELINE configs[4] shape: 1 image, short prompt, bf16 weights; no EOS: every run produces NEW tokens).
+
+    python tools/decode_bench.py [NEW [WEIGHTS [BATCH]]]                         greedy (the form of before)
+    python tools/decode_bench.py 256 bf16 1 --sample device --repeats 3          sampled decode, temperature 0.4, top_k 50, top_p 0.9, drawn by
+                                                                                 the HIP sampler (`device`) or by the torch warpers (`torch`)
+    python tools/decode_bench.py 256 bf16 8 --sample off,torch,device --repeats 3    A/B: the modes alternate inside every repeat
+"""
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from lhrs_bot_amd.unibind import UniBind
 
-new = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-weights = sys.argv[2] if len(sys.argv) > 2 else "bf16"
-B = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-model = UniBind(("rgb", "text"), None, device="cuda", llama_layers=32).init_random(seed=0).eval()
+ap = argparse.ArgumentParser()
+ap.add_argument("new", nargs="?", type=int, default=64)
+ap.add_argument("weights", nargs="?", default="bf16")
+ap.add_argument("batch", nargs="?", type=int, default=1)
+ap.add_argument("--sample", default="off", help="off = greedy; torch | device = do_sample=True with that sampler; a comma list alternates them")
+ap.add_argument("--repetition-penalty", type=float, default=1.0)
+ap.add_argument("--repeats", type=int, default=1, help="timed runs (one line each; one model, one warm-up)")
+ap.add_argument("--layers", type=int, default=32)
+a = ap.parse_args()
+new, weights, B = a.new, a.weights, a.batch
+model = UniBind(("rgb", "text"), None, device="cuda", llama_layers=a.layers).init_random(seed=0).eval()
 ids = torch.randint(3, 32000, (B, 60)); ids[:, 0] = 1; ids[:, 1] = -200
 rgb = torch.randn(B, 3, 224, 224)
-model.generate(ids, images=rgb, do_sample=False, max_new_tokens=4, weights=weights)
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-out = model.generate(ids, images=rgb, do_sample=False, max_new_tokens=new, weights=weights)
-torch.cuda.synchronize()
-dt = time.perf_counter() - t0
-print(f"[{weights}, batch {B}] {B}x{new} new tokens in {dt:.3f}s = {B*new/dt:.1f} tok/s (incl. ViT+pooler+prefill of {60-1+144} positions); HBM roofline " + ("6.74 GB/token @ 8 TB/s = 1190 tok/s" if weights == "fp8" else "13.5 GB/token @ 8 TB/s = 590 tok/s") + " per sequence")
+modes = a.sample.split(",")
+assert all(m in ("off", "torch", "device") for m in modes), a.sample
+
+
+def kwargs(mode):
+    # eos_token_id=None in EVERY mode (as bench.py --decode and cli_qa.py --synthetic-prompt time it): with an EOS the host synchronises on every
+    # token and torch operators run between the graph replay and decode_emit, whoever picks the token
+    kw = dict(do_sample=False, weights=weights, eos_token_id=None)
+    if mode != "off":
+        kw.update(do_sample=True, temperature=0.4, top_k=50, top_p=0.9, sampler=mode, seed=0)
+    if a.repetition_penalty != 1.0:
+        kw.update(repetition_penalty=a.repetition_penalty)
+    return kw
+
+
+for mode in modes:
+    model.generate(ids, images=rgb, max_new_tokens=4, **kwargs(mode))
+for _ in range(a.repeats):
+    for mode in modes:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = model.generate(ids, images=rgb, max_new_tokens=new, **kwargs(mode))
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        n_new = out.shape[1]
+        name = "greedy" if mode == "off" else f"sampled/{mode}"
+        print(f"[{weights}, batch {B}, {name}] {B}x{n_new} new tokens in {dt:.3f}s = {B*n_new/dt:.1f} tok/s (incl. ViT+pooler+prefill of {60-1+144} positions); HBM roofline " + ("6.74 GB/token @ 8 TB/s = 1190 tok/s" if weights == "fp8" else "13.5 GB/token @ 8 TB/s = 590 tok/s") + " per sequence", flush=True)
