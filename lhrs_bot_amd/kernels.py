@@ -322,6 +322,7 @@ def layernorm_fwd(x, gamma, beta, eps=1e-5, save_stats=False, out=None):
 def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma=None, dbeta=None, accumulate=False, need_dx=True, add=None, out=None):
     rows, cols = x.shape
     dx = (torch.empty_like(x) if out is None else out) if need_dx else None
+    assert add is None or dx is None or add.stride(0) == dx.stride(0), "layernorm_bwd: add is read with dx's row stride"
     part = None
     if dgamma is not None:
         nblk = _L().lhrs_layernorm_bwd_nblk(rows)
@@ -347,6 +348,7 @@ def rmsnorm_bwd(dy, x, w, rstd=None, add=None, eps=1e-5, out=None):
     rows, cols = x.shape
     assert dy.is_contiguous() and x.is_contiguous()
     dx = torch.empty_like(x) if out is None else out
+    assert dx.is_contiguous() and (add is None or add.is_contiguous()), "rmsnorm_bwd: add and out are read / written with row stride cols"
     st = _L().lhrs_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(), _p(rstd), _p(add), dx.data_ptr(), rows, cols, eps,
                                _stream())
     _lib.check(st, "rmsnorm_bwd")
@@ -370,6 +372,7 @@ def rmsnorm_bwd_q(dy, x, w, rstd=None, add=None, eps=1e-5, out=None):
     rows, cols = x.shape
     assert dy.is_contiguous() and x.is_contiguous()
     dx = torch.empty_like(x) if out is None else out
+    assert dx.is_contiguous() and (add is None or add.is_contiguous()), "rmsnorm_bwd_q: add and out are read / written with row stride cols"
     d8 = torch.empty((rows, cols), device=x.device, dtype=torch.uint8)
     sc = torch.empty(rows, device=x.device, dtype=torch.float32)
     st = _L().lhrs_rmsnorm_bwd_q(dy.data_ptr(), x.data_ptr(), w.data_ptr(), _p(rstd), _p(add), dx.data_ptr(), d8.data_ptr(), sc.data_ptr(),

@@ -8,7 +8,7 @@ import torch
 
 from oracle import lhrs_oracle as O
 from oracle import params as OP
-from oracle.optim_oracle import adamw_step_ref
+from oracle.optim_oracle import adamw_step_ref, adan_step_ref
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -153,6 +153,33 @@ def test_adamw_restatement_matches_torch():
         opt.step()
         adamw_step_ref(st, grad, step, lr=1e-3, wd=0.1)
         assert (w.detach() - st["p"]).abs().max() < 1e-12
+
+
+def test_adan_restatement_prox_and_no_prox_forms():
+    """Adan's two weight-decay forms (the paper's Algorithm 1 and timm's no_prox switch) share every moment and the update u; they differ in
+    the last line alone: no_prox  w <- w (1 - lr wd) - lr u,  prox  w <- (w - lr u) / (1 + lr wd).  Equal at wd = 0; at wd > 0, from a
+    shared state, the prox result is (w - lr u) / (1 + lr wd) with the lr u that the no_prox line used."""
+    n, lr, wd = 500, 1e-2, 0.05
+    g = torch.Generator().manual_seed(1)
+    p0 = torch.randn(n, generator=g, dtype=torch.float64)
+    new = lambda: dict(p=p0.clone(), m=torch.zeros(n, dtype=torch.float64), v=torch.zeros(n, dtype=torch.float64), n=torch.zeros(n, dtype=torch.float64), pre=None)
+    a0, b0, a, b = new(), new(), new(), new()
+    for step in range(1, 5):
+        grad = torch.randn(n, generator=g, dtype=torch.float64)
+        adan_step_ref(a0, grad, step, lr, wd=0.0, no_prox=True)
+        adan_step_ref(b0, grad, step, lr, wd=0.0, no_prox=False)
+        assert torch.equal(a0["p"], b0["p"])
+        w = b["p"].clone()
+        shared = {k: (None if v is None else v.clone()) for k, v in b.items()}
+        adan_step_ref(b, grad, step, lr, wd=wd, no_prox=False)
+        adan_step_ref(shared, grad, step, lr, wd=wd, no_prox=True)
+        for k in ("m", "v", "n", "pre"):
+            assert torch.equal(b[k], shared[k]), k
+        lr_u = w * (1 - lr * wd) - shared["p"]                       # lr * update, from the no_prox line
+        assert (b["p"] - (w - lr_u) / (1 + lr * wd)).abs().max() < 1e-14
+        assert (b["p"] - shared["p"]).abs().max() > 1e-6             # and the two forms do differ
+        adan_step_ref(a, grad, step, lr, wd=wd, no_prox=True)
+    assert (a["p"] - b["p"]).abs().max() > 1e-6
 
 
 def test_batched_left_padded_generate_matches_reference():
