@@ -50,6 +50,9 @@ def parse_option(args=None):
                         "device: every turn draws from the Philox stream of --seed starting at step 0, so the same conversation replays to the "
                         "same answers (torch: one global generator runs on across the turns)")
     p.add_argument("--repetition-penalty", type=float, default=1.0, help="HF repetition_penalty over the generated tokens (the web UI uses 1.05)")
+    p.add_argument("--num-beams", type=int, default=1, help="HF num_beams: > 1 answers by deterministic beam search on the device (no sampling, no token "
+                                                            "stream: the answer is printed when the search ends); batch * num_beams <= 16")
+    p.add_argument("--length-penalty", type=float, default=1.0, help="HF length_penalty of the beam search: hypotheses score sum(log p) / length ** penalty")
     cfg = ConfigDict(p.parse_args(wandb=True, args=args))
     opts = cfg.get("opts") or []
     if len(opts) % 2:
@@ -120,7 +123,8 @@ def main(config):
         g = torch.Generator().manual_seed(int(config.seed))
         ids = torch.randint(3, 32000, (1, T), generator=g)
         ids[0, 0], ids[0, 1] = 1, IMAGE_TOKEN_INDEX
-        kw = dict(images=image_tensor, do_sample=False, use_cache=True, weights=weights, eos_token_id=None)
+        kw = dict(images=image_tensor, do_sample=False, use_cache=True, weights=weights, eos_token_id=None, num_beams=int(config.num_beams),
+                  length_penalty=float(config.length_penalty))
         model.generate(ids, max_new_tokens=4, **kw)  # graph capture + allocator warm-up
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -153,9 +157,15 @@ def main(config):
         stop_str = conv.sep if conv.sep_style != SeparatorStyle.TWO else conv.sep2
         stopping_criteria = KeywordsStoppingCriteria([stop_str], tokenizer, input_ids)
         with torch.inference_mode():
-            output_ids = model.generate(input_ids, images=image_tensor, do_sample=True, max_new_tokens=int(config.max_new_tokens), temperature=0.4,
-                                        streamer=_Streamer(tokenizer), use_cache=True, stopping_criteria=[stopping_criteria], weights=weights,
-                                        sampler=config.sampler, repetition_penalty=float(config.repetition_penalty), seed=int(config.seed))
+            if int(config.num_beams) > 1:   # beam search stops on the tokenizer's EOS, on the device: no streamer, no host stopping criteria
+                output_ids = model.generate(input_ids, images=image_tensor, do_sample=False, max_new_tokens=int(config.max_new_tokens), use_cache=True,
+                                            weights=weights, num_beams=int(config.num_beams), length_penalty=float(config.length_penalty),
+                                            repetition_penalty=float(config.repetition_penalty))
+                print(tokenizer.decode(output_ids[0], skip_special_tokens=True).strip())
+            else:
+                output_ids = model.generate(input_ids, images=image_tensor, do_sample=True, max_new_tokens=int(config.max_new_tokens), temperature=0.4,
+                                            streamer=_Streamer(tokenizer), use_cache=True, stopping_criteria=[stopping_criteria], weights=weights,
+                                            sampler=config.sampler, repetition_penalty=float(config.repetition_penalty), seed=int(config.seed))
         outputs = tokenizer.decode(output_ids[0]).strip().split("<s>")[-1].strip()
         conv.messages[-1][-1] = outputs
         if config.debug:

@@ -315,6 +315,29 @@ int lhrs_sample_rows(const float* logits, long ld, long* out, int n, int V,
                      float repetition_penalty /* 1: off */, unsigned* seen /* [n][(V+31)/32] bitmap, may be NULL iff penalty == 1 */,
                      unsigned long long seed, const int* step_dev /* may be NULL */, long step_host,
                      long long* weights_out /* [n][V], tests only, NULL in the product */, void* stream);
+/* beam search (HF generate num_beams > 1, do_sample=False: the web UI's answer_prepare kwargs), three launches per token between the model step
+ * and lhrs_decode_emit.  bstate: int32 [4] = {t = tokens generated before this step, done, -, -}; once done is set all three change nothing.
+ * hist: int32 [2][rows][max_new] token history of the running beams, buffer t & 1 is current.
+ * beam_topk_rows: one workgroup per running beam (n_rows = B * num_beams, V <= 32768): total = log_softmax(logits)[i] (seen tokens of the beam's own
+ * history: * repetition_penalty) + run_score[row]; the row's top K = 2 * num_beams as cand_score / cand_tok [n_rows][K], descending, lower token
+ * first among equal totals. */
+int lhrs_beam_topk_rows(const float* logits, long ld, int n_rows, int V, int K, const float* run_score, float repetition_penalty,
+                        const int* hist /* NULL allowed iff penalty == 1 */, int max_new, const int* bstate /* NULL: t = 0, not done */,
+                        float* cand_score, int* cand_tok, void* stream);
+/* beam_step: one wave per batch row.  Merges the num_beams * K candidates of a row (ties: lower beam * V + token), then HF's step: a candidate
+ * hits if its token is eos_token_id (-1: none) or t + 1 == max_new; the next running beams are the best num_beams that did not hit (run_score,
+ * parent, next_ids [B * nb], hist); hits among the first num_beams ranks enter the finished set with total / len_pow[t + 1] (len_pow[n] =
+ * n ** length_penalty, fp32 [max_new + 1]) unless the row's heuristic is off or early_stopping and the set was full; fin_score / fin_len [B * nb]
+ * sorted by score (init -1e9 / 0), fin_slot [B * nb] (init 0..nb-1 per row) = row of fin_seq [B * nb][max_new] that holds the hypothesis;
+ * heur [B] (init 1): sticky "a running beam can still beat the worst finished one"; bstate[0] += 1, bstate[1] = HF's batch-wide stop. */
+int lhrs_beam_step(const float* cand_score, const int* cand_tok, int B, int num_beams, int V, int max_new, int eos_token_id, int early_stopping,
+                   const float* len_pow, float* run_score, int* parent, long* next_ids, int* hist, float* fin_score, int* fin_len,
+                   int* fin_slot, int* fin_seq, int* heur, int* bstate, void* stream);
+/* kv_beam_reorder: in place, for every cache base pointer of table [n_caches] (device array; bf16 [B * nb * max_ctx][d]) and every group b:
+ * row [b * nb + j] takes the positions [t0, t1) of row [b * nb + parent[b * nb + j]]; t1 = *t1_dev when given, else t1_host; the grid covers
+ * max_pos positions from t0.  An identity parent moves nothing.  done (NULL allowed): nothing moves once *done is set. */
+int lhrs_kv_beam_reorder(const long* table, int n_caches, int B, int num_beams, int max_ctx, int d, const int* parent, int t0,
+                         const int* t1_dev, int t1_host, int max_pos, const int* done, void* stream);
 int lhrs_cross_entropy(const void* logits, long ld, const int* target, float* row_loss, float* loss_out, void* dlogits,
                        long ld_d, int n, int V, void* stream);
 

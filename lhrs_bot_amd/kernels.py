@@ -725,6 +725,77 @@ def sample_rows(logits_f32, out=None, *, mode=0, temperature=1.0, top_k=0, top_p
     return out
 
 
+class BeamState:
+    """Device state of one beam search over B rows x nb beams (include/lhrs_hip.h: lhrs_beam_step), initialised as HF's _beam_search does."""
+
+    def __init__(self, B, nb, V, max_new, length_penalty, device):
+        R = B * nb
+        i32, f32 = dict(device=device, dtype=torch.int32), dict(device=device, dtype=torch.float32)
+        self.B, self.nb, self.V, self.max_new, self.K = B, nb, V, max_new, 2 * nb
+        self.bstate = torch.zeros(4, **i32)                       # {t, done, -, -}
+        run = torch.full((B, nb), -1.0e9, dtype=torch.float32)
+        run[:, 0] = 0.0
+        self.run_score = h2d(run.reshape(-1), device)
+        self.parent = torch.zeros(R, **i32)
+        self.hist = torch.zeros((2, R, max_new), **i32)
+        self.fin_score = torch.full((R,), -1.0e9, **f32)
+        self.fin_len = torch.zeros(R, **i32)
+        self.fin_slot = h2d(torch.arange(nb, dtype=torch.int32).repeat(B), device)
+        self.fin_seq = torch.zeros((R, max_new), **i32)
+        self.heur = torch.ones(B, **i32)
+        self.cand_score = torch.zeros((R, self.K), **f32)
+        self.cand_tok = torch.zeros((R, self.K), **i32)
+        # n ** length_penalty as HF forms it (a Python float) and as its fp32 division sees it
+        self.len_pow = h2d(torch.tensor([1.0] + [float(n) ** float(length_penalty) for n in range(1, max_new + 1)], dtype=torch.float64).to(torch.float32),
+                           device)
+
+    def buffers(self):
+        return (self.bstate, self.run_score, self.parent, self.hist, self.fin_score, self.fin_len, self.fin_slot, self.fin_seq, self.heur,
+                self.cand_score, self.cand_tok)
+
+
+def beam_topk_rows(logits_f32, st: BeamState, repetition_penalty=1.0):
+    """lhrs_beam_topk_rows: per running beam the top 2 * nb of log_softmax(logits) (+ penalty over the beam's history) + running score
+    -> st.cand_score / st.cand_tok [B * nb, K]"""
+    n, V = logits_f32.shape
+    _req(logits_f32, torch.float32, "logits")
+    assert logits_f32.stride(1) == 1 and n == st.B * st.nb and V == st.V, f"logits {tuple(logits_f32.shape)} for B={st.B} nb={st.nb} V={st.V}"
+    _lib.check(_L().lhrs_beam_topk_rows(logits_f32.data_ptr(), logits_f32.stride(0), n, V, st.K, st.run_score.data_ptr(), float(repetition_penalty),
+                                        st.hist.data_ptr(), st.max_new, st.bstate.data_ptr(), st.cand_score.data_ptr(), st.cand_tok.data_ptr(),
+                                        _stream()), "beam_topk_rows")
+    return st.cand_score, st.cand_tok
+
+
+def beam_step(st: BeamState, next_ids, eos_token_id=None, early_stopping=False):
+    """lhrs_beam_step: merge st.cand_*, advance the running beams / finished set / flags of every row; next_ids int64 [B * nb] is where
+    decode_emit reads the tokens of the new running beams"""
+    _req(next_ids, torch.int64, "next_ids")
+    assert next_ids.is_contiguous() and next_ids.numel() == st.B * st.nb
+    _lib.check(_L().lhrs_beam_step(st.cand_score.data_ptr(), st.cand_tok.data_ptr(), st.B, st.nb, st.V, st.max_new,
+                                   -1 if eos_token_id is None else int(eos_token_id), int(bool(early_stopping)), st.len_pow.data_ptr(),
+                                   st.run_score.data_ptr(), st.parent.data_ptr(), next_ids.data_ptr(), st.hist.data_ptr(), st.fin_score.data_ptr(),
+                                   st.fin_len.data_ptr(), st.fin_slot.data_ptr(), st.fin_seq.data_ptr(), st.heur.data_ptr(), st.bstate.data_ptr(),
+                                   _stream()), "beam_step")
+
+
+def kv_cache_table(caches, device):
+    """int64 device array of the base pointers of every K and V cache (built once per session) for kv_beam_reorder"""
+    return h2d(torch.tensor([c.data_ptr() for kv in caches for c in kv], dtype=torch.int64), device)
+
+
+def kv_beam_reorder(table, B, nb, max_ctx, d, parent, t0, t1, max_pos, done=None):
+    """lhrs_kv_beam_reorder: cache row [b * nb + j] takes positions [t0, t1) of row [b * nb + parent[b * nb + j]], in place, in every cache of
+    `table`.  t1: an int, or a 1-element int32 device tensor (the session's context length: the captured launch stays valid for every step)."""
+    _req(table, torch.int64, "table")
+    _req(parent, torch.int32, "parent")
+    assert parent.is_contiguous() and parent.numel() == B * nb
+    t1_dev = t1 if isinstance(t1, torch.Tensor) else None
+    if t1_dev is not None:
+        _req(t1_dev, torch.int32, "t1")
+    _lib.check(_L().lhrs_kv_beam_reorder(table.data_ptr(), table.numel(), B, nb, max_ctx, d, parent.data_ptr(), int(t0), _p(t1_dev),
+                                         0 if t1_dev is not None else int(t1), int(max_pos), _p(done), _stream()), "kv_beam_reorder")
+
+
 def cross_entropy(logits, target, want_grad=True, inplace=True):
     n, V = logits.shape
     row_loss = torch.empty(n, device=logits.device, dtype=torch.float32)

@@ -950,7 +950,8 @@ class TextModal:
     @torch.no_grad()
     def generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p="default",
                  top_k="default", max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id="default",
-                 return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, **_kw):
+                 return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1,
+                 length_penalty=1.0, early_stopping=False, return_beam_scores=False, **_kw):
         """See `_generate`.  Two things happen here first: (1) `eos_token_id` defaults to the tokenizer's EOS, as HF `generate` stops on
         the generation config's EOS (pass None to disable); (2) if LoRA adapters are attached and not merged, the call runs on merged
         COPIES of the affected weights (`_lora_merged_layers`) and the base weights come back untouched."""
@@ -965,7 +966,8 @@ class TextModal:
         kw = dict(image_embedding=image_embedding, attention_mask=attention_mask, do_sample=do_sample, temperature=temperature, top_p=top_p,
                   top_k=top_k, max_new_tokens=max_new_tokens, use_cache=use_cache, stopping_criteria=stopping_criteria, streamer=streamer,
                   eos_token_id=eos_token_id, return_logits=return_logits, use_graph=use_graph, weights=weights, sampler=sampler, seed=seed,
-                  repetition_penalty=repetition_penalty)
+                  repetition_penalty=repetition_penalty, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
+                  return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1))
         if self.lora is None:
             return self._generate(input_ids, **kw)
         base_layers, base8, base_i8 = self.p["layers"], self.base8, self.base_int8
@@ -977,7 +979,8 @@ class TextModal:
 
     def _generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p=None,
                   top_k=None, max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id=None,
-                  return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, **_kw):
+                  return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1,
+                  length_penalty=1.0, early_stopping=False, return_beam_scores=False, num_return_sequences=1, **_kw):
         """TextModal.generate (text_modal.py:528-627): prefill over the spliced embeddings, then one token at a time with
         a KV cache; returns only the NEW token ids [B, n_new] (HF generate started from inputs_embeds).  Greedy
         (do_sample=False, the evaluation scripts' mode) runs entirely in HIP kernels; with do_sample=True the HIP-computed
@@ -995,6 +998,10 @@ class TextModal:
         row, which nothing reads any more."""
         if sampler not in ("torch", "device"):
             raise ValueError(f"sampler={sampler!r}: expected 'torch' or 'device'")
+        if int(num_beams) != 1:
+            return self._generate_beam(input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer,
+                                       eos_token_id, return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty,
+                                       early_stopping, return_beam_scores, num_return_sequences)
         pen = float(repetition_penalty)
         device_pick = (sampler == "device" and do_sample) or pen != 1.0
         if streamer is not None and getattr(streamer, "skip_prompt", False):
@@ -1124,6 +1131,114 @@ class TextModal:
         if streamer is not None:
             streamer.end()
         return (ids, torch.stack(all_logits, 1)) if return_logits else ids
+
+    def _generate_beam(self, input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer, eos_token_id,
+                       return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty, early_stopping, return_beam_scores,
+                       num_return_sequences):
+        """Deterministic beam search, HF `generate(num_beams=nb, do_sample=False)` (generation/utils.py _beam_search; the web UI's
+        answer_prepare kwargs): the prompt is prefilled ONCE per batch row into cache row b * nb and replicated to the row's other beams by
+        `hk.kv_beam_reorder`; every further token is one linear single-stream graph of [model step over B * nb rows, beam_topk_rows, beam_step,
+        kv_beam_reorder, decode_emit] (csrc/beam.hip).  All bookkeeping - running scores, parents, token histories, the finished set, the
+        early-stop heuristic and the batch-wide `done` word - lives on the device; the host reads `done` every fourth token when an EOS is set
+        (once done, the kernels change nothing, so the extra steps do not show) and never without one.  -> ids [B, L] of each row's best
+        hypothesis, pad_token_id past its end (, logits [B * nb, n, V] of the running beams)(, scores [B])."""
+        nb = int(num_beams)
+        if nb < 1:
+            raise ValueError(f"num_beams={num_beams!r}: must be >= 1")
+        if do_sample:
+            raise ValueError("do_sample=True with num_beams > 1 (beam-multinomial sampling) is not implemented")
+        if streamer is not None:
+            raise ValueError("streamer is not supported with num_beams > 1 (HF: beam search has no token stream)")
+        if stopping_criteria is not None:
+            raise ValueError("stopping_criteria is not supported with num_beams > 1: stopping is eos_token_id / max_new_tokens, on the device")
+        if int(num_return_sequences) != 1:
+            raise ValueError(f"num_return_sequences={num_return_sequences!r}: only the best hypothesis of each row is returned")
+        if early_stopping not in (False, True):
+            raise ValueError(f"early_stopping={early_stopping!r}: False or True ('never' is not implemented)")
+        embeds, _, mask, _ = self.prepare_inputs_for_multimodal(input_ids, attention_mask, None, image_embedding)
+        B, S0, d = embeds.shape
+        R = B * nb
+        if nb > 8 or R > 16:
+            raise ValueError(f"num_beams={nb} with batch {B}: batch * num_beams must be <= 16 (and num_beams <= 8)")
+        V, dev, pen = self.vocab, self.device, float(repetition_penalty)
+        max_ctx = S0 + max_new_tokens
+        if max_ctx > self.cos.shape[0]:
+            raise ValueError(f"prompt ({S0}) + max_new_tokens ({max_new_tokens}) exceeds the {self.cos.shape[0]} positions of the RoPE table")
+        kmask = kmask_r = None
+        if mask is not None and not bool(mask.bool().all()):   # left-padded prompts, as in _generate; every beam hides its row's padding
+            kmask = torch.ones((B, max_ctx), device=dev, dtype=torch.uint8)
+            kmask[:, :S0] = mask.to(device=dev, dtype=torch.uint8)
+            kmask_r = kmask.repeat_interleave(nb, 0).contiguous()
+        caches = [(torch.empty((R * max_ctx, d), device=dev, dtype=torch.bfloat16), torch.empty((R * max_ctx, d), device=dev, dtype=torch.bfloat16))
+                  for _ in range(len(self.p["layers"]))]
+        s = self._decode_session(R, max_ctx, caches, max_new_tokens, weights, kmask_r)
+        s.state[0], s.state[1] = S0, 0
+        st = hk.BeamState(B, nb, V, max_new_tokens, length_penalty, dev)
+        table = hk.kv_cache_table(caches, dev)
+
+        # ---- prefill: sequence b into cache row b * nb (a cache "row" of nb * max_ctx positions), logits of the last prompt position
+        desc = hk.make_desc([(b * S0, S0, b * nb * max_ctx, S0, S0, 0) for b in range(B)], dev)
+        x = embeds.reshape(B * S0, d)
+        for L, cache in zip(self.p["layers"], caches):
+            x = self._layer_step(L, x, B, S0, 0, cache, desc, nb * max_ctx, kmask)
+        hn = hk.rmsnorm_fwd(x.view(B, S0, d)[:, -1].contiguous(), self.p["norm_w"], self.eps)
+        logits = hk.gemm_nt(hn, self.p["lm_head"], out_f32=True).repeat_interleave(nb, 0).contiguous()   # the row's beams all start from it
+        all_logits = [logits] if return_logits else []
+
+        def beam_tail(lg, t0, t1):
+            hk.beam_topk_rows(lg, st, pen)
+            hk.beam_step(st, s.next_ids, eos_token_id, early_stopping)
+            hk.kv_beam_reorder(table, B, nb, max_ctx, d, st.parent, t0, t1, S0 if t0 == 0 else max_new_tokens, done=st.bstate[1:2])
+            hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, R, max_new_tokens)
+
+        def step():
+            s.enqueue()
+            beam_tail(s.logits, S0, s.state[0:1])
+
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            beam_tail(logits, 0, S0)          # parents are all 0: replicates the prompt's cache to every beam of the row
+            n_done = 1
+            while n_done < max_new_tokens:
+                if use_graph and s.graph is None and n_done >= 2:  # one eager step first (lazy kernel attributes), then capture
+                    g = hk.HipGraph()
+                    g.begin()
+                    step()
+                    g.end()
+                    s.graph = g
+                    s.graph.launch()
+                elif s.graph is not None:
+                    s.graph.launch()
+                else:
+                    step()
+                if return_logits:
+                    all_logits.append(s.logits.clone())
+                n_done += 1
+                if eos_token_id is not None and n_done % 4 == 0 and int(st.bstate[1].item()):
+                    break
+        torch.cuda.current_stream().wait_stream(side)
+        # ---- the result of each row: its best finished hypothesis, else its best running beam (tiny host-side epilogue, once per call)
+        n = int(st.bstate[0].item())
+        fin_score, fin_len, fin_slot = st.fin_score.view(B, nb).cpu(), st.fin_len.view(B, nb).cpu(), st.fin_slot.view(B, nb).cpu()
+        fin_seq, hist, run = st.fin_seq.view(B, nb, -1).cpu(), st.hist[n & 1].view(B, nb, -1).cpu(), st.run_score.view(B, nb).cpu()
+        rows, scores = [], []
+        for b in range(B):
+            if int(fin_len[b, 0]) > 0:
+                rows.append(fin_seq[b, int(fin_slot[b, 0]), :int(fin_len[b, 0])])
+                scores.append(float(fin_score[b, 0]))
+            else:
+                rows.append(hist[b, 0, :n])
+                scores.append(float(run[b, 0]))
+        ids = torch.full((B, max(len(r) for r in rows)), int(self.tokenizer.pad_token_id), dtype=torch.int64)
+        for b, r in enumerate(rows):
+            ids[b, :len(r)] = r
+        out = (ids.to(dev),)
+        if return_logits:
+            out += (torch.stack(all_logits[:n], 1),)
+        if return_beam_scores:
+            out += (torch.tensor(scores, dtype=torch.float32, device=dev),)
+        return out if len(out) > 1 else out[0]
 
     # ------------------------------------------------------------------ backward (activation gradients only)
     def backward(self, loss_scale: float = 1.0, need_input_grad: bool = True, on_layer_ready=None):

@@ -4,6 +4,8 @@
     python tools/decode_bench.py 256 bf16 1 --sample device --repeats 3          sampled decode, temperature 0.4, top_k 50, top_p 0.9, drawn by
                                                                                  the HIP sampler (`device`) or by the torch warpers (`torch`)
     python tools/decode_bench.py 256 bf16 8 --sample off,torch,device --repeats 3    A/B: the modes alternate inside every repeat
+    python tools/decode_bench.py 256 bf16 1 --num-beams 4 --repeats 3            beam search (batch x 4 rows through the weights), alternating
+                                                                                 with greedy at batch 4 x BATCH: the same rows, no beam kernels
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,35 +20,44 @@ ap.add_argument("--sample", default="off", help="off = greedy; torch | device = 
 ap.add_argument("--repetition-penalty", type=float, default=1.0)
 ap.add_argument("--repeats", type=int, default=1, help="timed runs (one line each; one model, one warm-up)")
 ap.add_argument("--layers", type=int, default=32)
+ap.add_argument("--num-beams", type=int, default=1, help="> 1: mode `beam` (generate(num_beams=N)) alternates with mode `rows` (greedy at batch N x BATCH)")
+ap.add_argument("--beam-only", action="store_true", help="with --num-beams: mode `beam` alone (kernel traces)")
 a = ap.parse_args()
 new, weights, B = a.new, a.weights, a.batch
 model = UniBind(("rgb", "text"), None, device="cuda", llama_layers=a.layers).init_random(seed=0).eval()
 ids = torch.randint(3, 32000, (B, 60)); ids[:, 0] = 1; ids[:, 1] = -200
 rgb = torch.randn(B, 3, 224, 224)
-modes = a.sample.split(",")
-assert all(m in ("off", "torch", "device") for m in modes), a.sample
+modes = a.sample.split(",") if a.num_beams == 1 else ["beam"] if a.beam_only else ["beam", "rows"]
+assert all(m in ("off", "torch", "device", "beam", "rows") for m in modes), a.sample
+ids_rows, rgb_rows = ids.repeat(a.num_beams, 1), rgb.repeat(a.num_beams, 1, 1, 1)   # mode `rows`: the prompt N times
 
 
 def kwargs(mode):
     # eos_token_id=None in EVERY mode (as bench.py --decode and cli_qa.py --synthetic-prompt time it): with an EOS the host synchronises on every
     # token and torch operators run between the graph replay and decode_emit, whoever picks the token
     kw = dict(do_sample=False, weights=weights, eos_token_id=None)
-    if mode != "off":
+    if mode == "beam":
+        kw.update(num_beams=a.num_beams)
+    elif mode not in ("off", "rows"):
         kw.update(do_sample=True, temperature=0.4, top_k=50, top_p=0.9, sampler=mode, seed=0)
     if a.repetition_penalty != 1.0:
         kw.update(repetition_penalty=a.repetition_penalty)
     return kw
 
 
+def inputs(mode):
+    return (ids_rows, rgb_rows) if mode == "rows" else (ids, rgb)
+
+
 for mode in modes:
-    model.generate(ids, images=rgb, max_new_tokens=4, **kwargs(mode))
+    model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=4, **kwargs(mode))
 for _ in range(a.repeats):
     for mode in modes:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = model.generate(ids, images=rgb, max_new_tokens=new, **kwargs(mode))
+        out = model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=new, **kwargs(mode))
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         n_new = out.shape[1]
-        name = "greedy" if mode == "off" else f"sampled/{mode}"
+        name = {"off": "greedy", "beam": f"beam search x{a.num_beams}", "rows": f"greedy, {out.shape[0]} rows"}.get(mode, f"sampled/{mode}")
         print(f"[{weights}, batch {B}, {name}] {B}x{n_new} new tokens in {dt:.3f}s = {B*n_new/dt:.1f} tok/s (incl. ViT+pooler+prefill of {60-1+144} positions); HBM roofline " + ("6.74 GB/token @ 8 TB/s = 1190 tok/s" if weights == "fp8" else "13.5 GB/token @ 8 TB/s = 590 tok/s") + " per sequence", flush=True)
