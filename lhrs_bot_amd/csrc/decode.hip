@@ -181,8 +181,9 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_kernel(const bf16_t* __rest
   constexpr int WSTEP = PK ? 512 : 32;       // elements between consecutive 32-k steps of this lane
   constexpr int U = 4;                       // k-steps (of 32) in flight per wave
   i32x4 wreg[U];
+  const int nsteps = kq / 32;                // 1 (K 128 at 4 waves, K 256 at 8) or more: the preload stays inside the wave's own slice
 #pragma unroll
-  for (int u = 0; u < U; ++u) wreg[u] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(wp + u * WSTEP));  // kq >= 128
+  for (int u = 0; u < U; ++u) wreg[u] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(wp + (long)min(u, nsteps - 1) * WSTEP));
   for (int b = 0; b < (PRO == 0 ? 0 : NB); ++b) {  // PRO 0: x is read straight from L2 into the B fragments, nothing to stage
     if (PRO == 2) {
       for (int c = tid; c < nch; c += NW * 64) {
@@ -215,7 +216,6 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_kernel(const bf16_t* __rest
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const bf16_t* xq = (PRO == 0 ? x + (long)min(fr, NB - 1) * ldx : xs + (long)min(fr, NB - 1) * K) + wave * kq + fg * 8;
   const bool live = fr < NB;
-  const int nsteps = kq / 32;
   for (int s0 = 0; s0 < nsteps; s0 += U) {
     i32x4 wnext[U];
     bf16x8 xfrag[U];
@@ -979,8 +979,13 @@ extern "C" int lhrs_gemv(const void* W, long ldw, const float* wscale, int w_for
   LHRS_REQUIRE(B <= 8 || (!w_fp8 && K % 128 == 0), "gemv: batches above 8 need bf16 weights and K %% 128 == 0");
   LHRS_REQUIRE(w_fp8 ? (ldw % 16 == 0 && wscale != nullptr) : (w_packed || ldw % 8 == 0), "gemv: weight stride / scales");
   LHRS_REQUIRE(prologue >= 0 && prologue <= 2 && (prologue != 1 || norm_w != nullptr), "gemv: prologue %d", prologue);
-  int bmax = (int)((152L * 1024) / ((long)K * 2));
-  if (!w_fp8 && prologue == 0 && B >= 2 && K % 128 == 0) bmax = 16;  // the MFMA kernel reads x from L2: no LDS limit
+  // staged activations: 152 KiB, and together with the static LDS of the kernel the chunk goes to (the MFMA kernel's part[NW][16][17] +
+  // red[NW] = 8736 B at 8 waves, 4368 B at 4) no more than the 160 KiB of a CU
+  const bool mfma = !w_fp8 && B >= 2 && K % 128 == 0;
+  const long lds_static = mfma ? (K % 256 == 0 ? 8 : 4) * (16 * 17 + 1) * 4L : 16;
+  const long lds_x = 152L * 1024 < 160L * 1024 - lds_static ? 152L * 1024 : 160L * 1024 - lds_static;
+  int bmax = (int)(lds_x / ((long)K * 2));
+  if (mfma && prologue == 0) bmax = 16;  // the MFMA kernel reads x from L2: no LDS limit
   LHRS_REQUIRE(bmax >= 1, "gemv: one activation vector does not fit LDS (K=%d)", K);
   const long esz = out_f32 ? 4 : 2;
   hipStream_t s = (hipStream_t)stream;
