@@ -6,7 +6,8 @@ flag-compatible (`-c Config/multi_modal_eval.yaml --model-path <FINAL.pt dir> --
     KeywordsStoppingCriteria(["</s>"]) -> model.generate(do_sample=True, temperature=0.4, max_new_tokens=512, streamer=...)
 
 The prefill runs on the GEMM path, the per-token step is one captured hipGraph (lhrs_bot_amd/text.py `_decode_session`);
-`bits: 8` in the YAML (or `--opts bits 8`) streams e4m3 weights through the MFMA GEMV.
+`bits: 8` in the YAML (or `--opts bits 8`) streams e4m3 weights through the MFMA GEMV; `--decode-weights 4bit` with `bits: 4` streams
+the NF4 / FP4 codes of the 4-bit base (lhrs_gemv4).
 
 Imports and call order follow /root/reference cli_qa.py:10-22, 84-193 over the `lhrs.*` surface.  Weights / tokenizer come from the paths
 in the YAML (`text.path`, `rgb_vision.vit_name`); when they are not on disk the towers are random-initialised and the word-hash
@@ -52,6 +53,11 @@ def parse_option(args=None):
     p.add_argument("--repetition-penalty", type=float, default=1.0, help="HF repetition_penalty over the generated tokens (the web UI uses 1.05)")
     p.add_argument("--num-beams", type=int, default=1, help="HF num_beams: > 1 answers by deterministic beam search on the device (no sampling, no token "
                                                             "stream: the answer is printed when the search ends); batch * num_beams <= 16")
+    p.add_argument("--decode-weights", default=None, choices=["bf16", "fp8", "4bit"],
+                   help="what the single-token step streams (default: fp8 iff `bits: 8`, else bf16); 4bit reads the NF4 / FP4 codes of the `bits: 4` "
+                        "base directly and requires it; if the decoder is not on that base yet (an evaluation run has not been through "
+                        "prepare_for_training) it is put there first with the YAML's quant_type / double_quant, so the prefill too reads "
+                        "the dequantised weights, as every product of the reference's Linear4bit does")
     p.add_argument("--length-penalty", type=float, default=1.0, help="HF length_penalty of the beam search: hypotheses score sum(log p) / length ** penalty")
     cfg = ConfigDict(p.parse_args(wandb=True, args=args))
     opts = cfg.get("opts") or []
@@ -106,7 +112,13 @@ def main(config):
         model.text.tokenizer = transformers.AutoTokenizer.from_pretrained(config.tokenizer_path, use_fast=False)
     tokenizer = model.text.tokenizer
     model.eval()
-    weights = "fp8" if int(config.get("bits", 16) or 16) == 8 else "bf16"
+    bits = int(config.get("bits", 16) or 16)
+    weights = config.get("decode_weights") or ("fp8" if bits == 8 else "bf16")
+    if weights == "4bit":
+        if bits != 4:
+            raise ValueError("--decode-weights 4bit requires `bits: 4` in the YAML (or --opts bits 4)")
+        if not model.text.base4:   # bits: 4 selects the storage in prepare_for_training; an evaluation run has not been through it
+            model.text.quantize_base(4, quant_type=str(config.get("quant_type", "nf4")), double_quant=bool(config.get("double_quant", True)))
 
     if config.get("image_file"):
         image = load_image(config.image_file)

@@ -351,6 +351,14 @@ int lhrs_gemv_bf16(const void* W, long ldw, const void* x, long ldx, const void*
 int lhrs_gemv(const void* W, long ldw, const float* wscale, int w_format, const void* x, long ldx, int prologue, const void* norm_w,
               float eps, const void* residual, long ldr, void* y, long ldy, int B, int N, int K, int out_f32, void* stream);
 int lhrs_repack_bf16_mfma(const void* W, long ldw, void* out, int N, int K, void* stream);
+/* decode from the 4-bit base (`bits: 4`): y[B, N] = pro(x)[B, K] . w[N, K]^T (+ residual) with w[n, k] = bf16(LEVEL[code[n, k]] * absmax[n][k / 64]) -
+ * one fp32 multiply and one rounding to bf16, the bits lhrs_dequant4_blocks stores - formed in registers from the codes of lhrs_quant4_blocks.
+ * codes: [N] rows of ldc BYTES (two codes per byte, even element in the high nibble; ldc % 16 == 0, 16-B aligned); absmax: [N] rows of lda
+ * floats, fp32 (double_quant statistics expanded by the caller); fp4 = 0: NF4 levels.  prologue / norm_w / eps / residual / out_f32 as lhrs_gemv.
+ * 1 <= B <= 16, K % 64 == 0; B == 1 and K % 128 != 0 (then B <= 8) run on the VALU kernel, B >= 2 with K % 128 == 0 on the MFMA kernel;
+ * batches exceeding the LDS are split as in lhrs_gemv */
+int lhrs_gemv4(const void* codes, long ldc, const float* absmax, long lda, int fp4, const void* x, long ldx, int prologue, const void* norm_w,
+               float eps, const void* residual, long ldr, void* y, long ldy, int B, int N, int K, int out_f32, void* stream);
 /* kernel A/B tests only: rows per wave / 1-KiB chunks per iteration of the batch-1 bf16 GEMV (0, 0 = the built-in shape rule) */
 int lhrs_gemv_set_tuning(int rows_per_wave, int chunks_per_iteration);
 int lhrs_quant_fp8_rows(const void* W, long ldw, void* W8, long ld8, float* scale, int N, int K, void* stream);

@@ -1129,6 +1129,63 @@ def dequant4_blocks(st, out=None):
     return out
 
 
+class Packed4:
+    """One fused decoder weight [N, K] as the decode GEMV reads it from the 4-bit base: `codes` uint8 [N, K/2] (two codes per byte, even element
+    in the high nibble), `absmax` fp32 [N, K/64], `fp4` (False: NF4 levels).  Made by `pack4_decode`."""
+
+    def __init__(self, codes, absmax, fp4, N, K):
+        self.codes, self.absmax, self.fp4 = codes, absmax, bool(fp4)
+        self.N, self.K = N, K
+        self.shape = (N, K)
+
+
+def pack4_decode(states, N: int, K: int) -> Packed4:
+    """The per-Linear 4-bit states of ONE fused weight (`L[name + "q4"]`: row-concatenated parts, each a contiguous row range) -> Packed4.
+    The codes are the stored ones, concatenated; the block statistics are `absmax_of` of each part, so `double_quant` statistics are expanded
+    to fp32 once, here.  Nothing is quantised anew."""
+    if K % 64 or not states:
+        raise ValueError(f"pack4_decode: K={K} must be a multiple of the block size 64 and the state list non-empty")
+    kinds = {st["quant_type"] for st in states}
+    if len(kinds) != 1:
+        raise ValueError(f"pack4_decode: the parts of one weight mix quant types {sorted(kinds)}")
+    codes = torch.cat([st["packed"].reshape(-1) for st in states]).reshape(-1, K // 2)
+    absmax = torch.cat([absmax_of(st).reshape(-1) for st in states]).reshape(-1, K // 64)
+    if codes.shape[0] != N or absmax.shape[0] != N:
+        raise ValueError(f"pack4_decode: the states hold {codes.shape[0]} rows of {K}, expected {N}")
+    return Packed4(codes.contiguous(), absmax.contiguous(), kinds.pop() == "fp4", N, K)
+
+
+def gemv4(W4: Packed4, x, out, K, *, prologue=PRO_NONE, norm_w=None, eps=1e-5, residual=None, out_f32=False):
+    """out[B, N] = pro(x)[B, K] @ w[N, K]^T (+ residual), w = bf16(level[code] * absmax) formed in registers from the 4-bit codes: what
+    `gemv_fused` computes on `dequant4_blocks` of the same states, up to the order of the fp32 sums.  Keywords as `gemv_fused`."""
+    if K != W4.K:
+        raise ValueError(f"gemv4: K={K} but the packed weight has K={W4.K}")
+    _req(W4.codes, torch.uint8, "gemv4 codes")
+    _req(W4.absmax, torch.float32, "gemv4 absmax")
+    _req(x, torch.bfloat16, "gemv4 x")
+    _req(out, torch.float32 if out_f32 else torch.bfloat16, "gemv4 out")
+    B = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != (2 * K if prologue == PRO_SWIGLU else K) or x.stride(1) != 1:
+        raise ValueError(f"gemv4: x {tuple(x.shape)} for K={K}, prologue {prologue} (SwiGLU reads [B, 2K]); rows must be dense")
+    if tuple(out.shape) != (B, W4.N) or out.stride(1) != 1:
+        raise ValueError(f"gemv4: out {tuple(out.shape)}, expected ({B}, {W4.N}) with dense rows")
+    if residual is not None:
+        _req(residual, torch.bfloat16, "gemv4 residual")
+        if tuple(residual.shape) != (B, W4.N) or residual.stride(1) != 1:
+            raise ValueError(f"gemv4: residual {tuple(residual.shape)}, expected ({B}, {W4.N}) with dense rows")
+    if prologue == PRO_RMSNORM:
+        if norm_w is None or norm_w.numel() != K or not norm_w.is_contiguous():
+            raise ValueError(f"gemv4: the RMSNorm prologue needs a contiguous norm_w of {K} elements")
+        _req(norm_w, torch.bfloat16, "gemv4 norm_w")
+    if tuple(W4.codes.shape) != (W4.N, K // 2) or tuple(W4.absmax.shape) != (W4.N, K // 64) or W4.codes.stride(1) != 1 or W4.absmax.stride(1) != 1:
+        raise ValueError(f"gemv4: codes {tuple(W4.codes.shape)} / absmax {tuple(W4.absmax.shape)} for a weight of shape {W4.shape}")
+    st = _L().lhrs_gemv4(W4.codes.data_ptr(), W4.codes.stride(0), W4.absmax.data_ptr(), W4.absmax.stride(0), int(W4.fp4), x.data_ptr(), x.stride(0),
+                         prologue, _p(norm_w), float(eps), _p(residual), residual.stride(0) if residual is not None else 0, out.data_ptr(),
+                         out.stride(0), B, W4.N, K, int(out_f32), _stream())
+    _lib.check(st, "gemv4")
+    return out
+
+
 class Int8Workspace:
     """Device scratch of the LLM.int8 activation side: outlier flags per input feature, the compacted outlier column list, meta = [columns
     found by the last call, that count rounded up to 64] and the persistent [N, KP + K] buffers of the dequantised outlier weight columns."""

@@ -277,7 +277,7 @@ class TextModal:
             self.quantize_base(4, quant_type=base4[0], double_quant=base4[1])   # peft re-quantises a merged Linear4bit the same way
 
     _W4_PARTS = {"qkv_w": 3, "o_w": 1, "gu_w": 2, "down_w": 1}   # reference Linears per fused weight (row-concatenated): 4-bit statistics are per Linear
-    DERIVED_SUFFIXES = ("p", "8", "8s", "8p", "i8", "i8s", "q4")   # decode re-tilings and e4m3 copies of a weight `<name>` / `<name>T`, rebuilt lazily from it
+    DERIVED_SUFFIXES = ("p", "8", "8s", "8p", "i8", "i8s", "q4", "4p")   # decode re-tilings and e4m3 copies of a weight `<name>` / `<name>T`, rebuilt lazily from it
 
     def _drop_derived(self, L) -> None:
         """Forget every tensor that was computed FROM a decoder weight of layer dict `L` (decode re-tilings, e4m3 copies): after the weight
@@ -772,6 +772,16 @@ class TextModal:
                 L[k + "p"] = hk.repack_bf16_mfma(L[k])
         self.p["lm_headp"] = hk.repack_bf16_mfma(self.p["lm_head"])
 
+    def pack4_decode(self):
+        """Decode-only form of the 4-bit base (`weights="4bit"`): per fused weight the stored codes of its reference Linears side by side and
+        their block statistics in fp32 (`hk.pack4_decode`: +3.6 GB next to the `q4` states; nothing is quantised anew).  lm_head is not
+        quantised in the reference and has no 4-bit form."""
+        if not self.base4:
+            raise ValueError("pack4_decode: the decoder is not on the 4-bit base - call quantize_base(4, quant_type, double_quant) first")
+        for L in self.p["layers"]:
+            for k in self._W4_PARTS:
+                L[k + "4p"] = hk.pack4_decode(L[k + "q4"], *L[k].shape)
+
     def quantize_base(self, bits: int = 8, scheme: str = "e4m3", quant_type: str = "nf4", double_quant: bool = True):
         """`bits: 8` of Config/multi_modal_stage{2,3}.yaml (text_modal.py:91-131: the reference loads the frozen LLaMA through bitsandbytes
         LLM.int8 for stages 2/3; lm_head stays 16-bit there and here).  Two schemes:
@@ -854,18 +864,31 @@ class TextModal:
         s.pos = torch.zeros(B, device=dev, dtype=torch.int32)
         scale = 1.0 / math.sqrt(hd)
 
-        fp8 = weights == "fp8"
+        if weights not in ("bf16", "fp8", "4bit"):
+            raise ValueError(f"weights={weights!r}: expected 'bf16', 'fp8' or '4bit'")
+        fp8, w4 = weights == "fp8", weights == "4bit"
         if fp8 and "qkv_w8p" not in self.p["layers"][0]:
             self.pack_fp8_decode()
+        if w4:  # the decoder linears stream the 4-bit codes (hk.gemv4); lm_head is not quantised in the reference and stays bf16
+            if not self.base4:
+                raise ValueError('weights="4bit" needs the 4-bit base: quantize_base(4, quant_type, double_quant) (YAML `bits: 4`)')
+            if "qkv_w4p" not in self.p["layers"][0]:
+                self.pack4_decode()
 
         packed16 = not fp8 and B >= 2 and d % 128 == 0 and ff % 128 == 0  # batched bf16: the MFMA GEMV on re-tiled weights
-        if packed16 and "qkv_wp" not in self.p["layers"][0]:
+        if packed16 and w4:  # lm_head alone: pack_bf16_decode() would add 13.5 GB of re-tiled decoder weights that this mode never reads
+            if "lm_headp" not in self.p:
+                self.p["lm_headp"] = hk.repack_bf16_mfma(self.p["lm_head"])
+        elif packed16 and "qkv_wp" not in self.p["layers"][0]:
             self.pack_bf16_decode()
 
         def W(L, name):  # (weight, per-row scale or None)
+            if w4:
+                return L[name + "4p"], None
             return (L[name + "8p"], L[name + "8s"]) if fp8 else (L[name + "p"] if packed16 else L[name], None)
 
-        batched = B >= 4 and not fp8  # the MFMA weight stream reads x from L2: norm / SwiGLU run once, not once per block (pays from batch 4)
+        # the MFMA weight streams (bf16 and 4-bit alike) read x from L2 with prologue 0: norm / SwiGLU run once, not once per block (pays from batch 4)
+        batched = B >= 4 and not fp8
         if batched:
             s.hn = torch.zeros((B, d), device=dev, dtype=bf)
             s.actb = torch.zeros((B, ff), device=dev, dtype=bf)
@@ -893,6 +916,9 @@ class TextModal:
             elif batched and pro == hk.PRO_SWIGLU:
                 hk.swiglu_fwd(x_in, ff, out=s.actb)
                 x_in, pro = s.actb, hk.PRO_NONE
+            if isinstance(w, hk.Packed4):
+                hk.gemv4(w, x_in, out, K, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
+                return
             hk.gemv_fused(w, x_in, out, K, wscale=sc, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
 
         # split-context attention (lhrs_decode_attn_split): 128-key slices, one workgroup each, so that a long context streams through
@@ -954,7 +980,12 @@ class TextModal:
                  length_penalty=1.0, early_stopping=False, return_beam_scores=False, **_kw):
         """See `_generate`.  Two things happen here first: (1) `eos_token_id` defaults to the tokenizer's EOS, as HF `generate` stops on
         the generation config's EOS (pass None to disable); (2) if LoRA adapters are attached and not merged, the call runs on merged
-        COPIES of the affected weights (`_lora_merged_layers`) and the base weights come back untouched."""
+        COPIES of the affected weights (`_lora_merged_layers`) and the base weights come back untouched.
+
+        `weights`: what the single-token step streams - "bf16" (default, whatever the base), "fp8" (e4m3 copies on the block-scaled MFMA) or
+        "4bit" (the codes and block statistics of `quantize_base(4)` through `hk.gemv4`; the decoder linears then compute what "bf16" computes
+        on the dequantised weights up to the order of the fp32 sums; lm_head stays bf16).  "4bit" raises ValueError without the 4-bit base and
+        with un-merged adapters."""
         if eos_token_id == "default":
             eos_token_id = getattr(self.tokenizer, "eos_token_id", None)
         # sampling defaults of the reference's callers: HF GenerationConfig top_k = 50 and the Llama-2 generation_config.json top_p = 0.9
@@ -970,6 +1001,9 @@ class TextModal:
                   return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1))
         if self.lora is None:
             return self._generate(input_ids, **kw)
+        if weights == "4bit":
+            raise ValueError('weights="4bit" with un-merged LoRA adapters: generate() then runs on merged 16-bit COPIES, which have no 4-bit form - '
+                             'call merge_lora() first (it re-quantises the merged weights, as peft does for a merged Linear4bit)')
         base_layers, base8, base_i8 = self.p["layers"], self.base8, self.base_int8
         self.p["layers"], self.base8, self.base_int8 = self._lora_merged_layers(), False, False   # merged 16-bit copies: no 8-bit operands of them exist
         try:

@@ -6,6 +6,10 @@
     python tools/decode_bench.py 256 bf16 8 --sample off,torch,device --repeats 3    A/B: the modes alternate inside every repeat
     python tools/decode_bench.py 256 bf16 1 --num-beams 4 --repeats 3            beam search (batch x 4 rows through the weights), alternating
                                                                                  with greedy at batch 4 x BATCH: the same rows, no beam kernels
+    python tools/decode_bench.py 256 bf16,fp8,4bit 1 --repeats 3                 A/B of the weight formats: the entries of WEIGHTS alternate inside
+                                                                                 every repeat.  With `4bit` in the list the model is put on the
+                                                                                 4-bit base (quantize_base(4, nf4, double_quant)) before the warm-up;
+                                                                                 `bf16` then streams the dequantised weights: same bytes, same speed
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,16 +27,32 @@ ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--num-beams", type=int, default=1, help="> 1: mode `beam` (generate(num_beams=N)) alternates with mode `rows` (greedy at batch N x BATCH)")
 ap.add_argument("--beam-only", action="store_true", help="with --num-beams: mode `beam` alone (kernel traces)")
 a = ap.parse_args()
-new, weights, B = a.new, a.weights, a.batch
+new, B = a.new, a.batch
+weight_modes = a.weights.split(",")
+assert all(w in ("bf16", "fp8", "4bit") for w in weight_modes), a.weights
 model = UniBind(("rgb", "text"), None, device="cuda", llama_layers=a.layers).init_random(seed=0).eval()
 ids = torch.randint(3, 32000, (B, 60)); ids[:, 0] = 1; ids[:, 1] = -200
 rgb = torch.randn(B, 3, 224, 224)
 modes = a.sample.split(",") if a.num_beams == 1 else ["beam"] if a.beam_only else ["beam", "rows"]
 assert all(m in ("off", "torch", "device", "beam", "rows") for m in modes), a.sample
 ids_rows, rgb_rows = ids.repeat(a.num_beams, 1), rgb.repeat(a.num_beams, 1, 1, 1)   # mode `rows`: the prompt N times
+if "4bit" in weight_modes:
+    model.text.quantize_base(4, quant_type="nf4", double_quant=True)
 
 
-def kwargs(mode):
+def token_bytes_4bit():
+    """bytes of weights one `4bit` token streams, from the tensors generate() reads (after the warm-up has built them): codes + fp32 block
+    statistics of every decoder linear, and the bf16 lm_head"""
+    def nbytes(t):
+        return t.numel() * t.element_size()
+    total = nbytes(model.text.p["lm_head"])
+    for L in model.text.p["layers"]:
+        for k in ("qkv_w", "o_w", "gu_w", "down_w"):
+            total += nbytes(L[k + "4p"].codes) + nbytes(L[k + "4p"].absmax)
+    return total
+
+
+def kwargs(mode, weights):
     # eos_token_id=None in EVERY mode (as bench.py --decode and cli_qa.py --synthetic-prompt time it): with an EOS the host synchronises on every
     # token and torch operators run between the graph replay and decode_emit, whoever picks the token
     kw = dict(do_sample=False, weights=weights, eos_token_id=None)
@@ -49,15 +69,20 @@ def inputs(mode):
     return (ids_rows, rgb_rows) if mode == "rows" else (ids, rgb)
 
 
-for mode in modes:
-    model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=4, **kwargs(mode))
+runs = [(mode, weights) for mode in modes for weights in weight_modes]
+for mode, weights in runs:
+    model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=4, **kwargs(mode, weights))
+roofline = {"fp8": "6.74 GB/token @ 8 TB/s = 1190 tok/s", "bf16": "13.5 GB/token @ 8 TB/s = 590 tok/s"}
+if "4bit" in weight_modes:
+    gb = token_bytes_4bit() / 1e9
+    roofline["4bit"] = f"{gb:.3g} GB/token @ 8 TB/s = {8000 / gb:.0f} tok/s"
 for _ in range(a.repeats):
-    for mode in modes:
+    for mode, weights in runs:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=new, **kwargs(mode))
+        out = model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=new, **kwargs(mode, weights))
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         n_new = out.shape[1]
         name = {"off": "greedy", "beam": f"beam search x{a.num_beams}", "rows": f"greedy, {out.shape[0]} rows"}.get(mode, f"sampled/{mode}")
-        print(f"[{weights}, batch {B}, {name}] {B}x{n_new} new tokens in {dt:.3f}s = {B*n_new/dt:.1f} tok/s (incl. ViT+pooler+prefill of {60-1+144} positions); HBM roofline " + ("6.74 GB/token @ 8 TB/s = 1190 tok/s" if weights == "fp8" else "13.5 GB/token @ 8 TB/s = 590 tok/s") + " per sequence", flush=True)
+        print(f"[{weights}, batch {B}, {name}] {B}x{n_new} new tokens in {dt:.3f}s = {B*n_new/dt:.1f} tok/s (incl. ViT+pooler+prefill of {60-1+144} positions); HBM roofline " + roofline[weights] + " per sequence", flush=True)
