@@ -58,6 +58,9 @@ def parse_option(args=None):
                         "base directly and requires it; if the decoder is not on that base yet (an evaluation run has not been through "
                         "prepare_for_training) it is put there first with the YAML's quant_type / double_quant, so the prefill too reads "
                         "the dequantised weights, as every product of the reference's Linear4bit does")
+    p.add_argument("--adapters", default="merged", choices=["merged", "live"],
+                   help="un-merged LoRA adapters (stage >= 1 with a TextLoRA/ loaded): merged = decode on merged 16-bit copies of the adapted weights; "
+                        "live = no copies, the adapters run next to the base weights of whatever --decode-weights streams (4bit included)")
     p.add_argument("--length-penalty", type=float, default=1.0, help="HF length_penalty of the beam search: hypotheses score sum(log p) / length ** penalty")
     cfg = ConfigDict(p.parse_args(wandb=True, args=args))
     opts = cfg.get("opts") or []
@@ -114,6 +117,7 @@ def main(config):
     model.eval()
     bits = int(config.get("bits", 16) or 16)
     weights = config.get("decode_weights") or ("fp8" if bits == 8 else "bf16")
+    adapters = str(config.get("adapters") or "merged")
     if weights == "4bit":
         if bits != 4:
             raise ValueError("--decode-weights 4bit requires `bits: 4` in the YAML (or --opts bits 4)")
@@ -136,7 +140,7 @@ def main(config):
         ids = torch.randint(3, 32000, (1, T), generator=g)
         ids[0, 0], ids[0, 1] = 1, IMAGE_TOKEN_INDEX
         kw = dict(images=image_tensor, do_sample=False, use_cache=True, weights=weights, eos_token_id=None, num_beams=int(config.num_beams),
-                  length_penalty=float(config.length_penalty))
+                  length_penalty=float(config.length_penalty), adapters=adapters)
         model.generate(ids, max_new_tokens=4, **kw)  # graph capture + allocator warm-up
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -145,7 +149,7 @@ def main(config):
         dt = time.perf_counter() - t0
         print(json.dumps({"metric": "cli_qa greedy generate tokens/s (ViT + projector + prefill included)", "value": round(out.shape[1] / dt, 1),
                           "unit": "tokens/s", "new_tokens": int(out.shape[1]), "prompt_positions": T - 1 + 144, "weights": weights,
-                          "seconds": round(dt, 3)}))
+                          "adapters": adapters, "seconds": round(dt, 3)}))
         return out
 
     if getattr(tokenizer, "is_synthetic", False):
@@ -172,12 +176,13 @@ def main(config):
             if int(config.num_beams) > 1:   # beam search stops on the tokenizer's EOS, on the device: no streamer, no host stopping criteria
                 output_ids = model.generate(input_ids, images=image_tensor, do_sample=False, max_new_tokens=int(config.max_new_tokens), use_cache=True,
                                             weights=weights, num_beams=int(config.num_beams), length_penalty=float(config.length_penalty),
-                                            repetition_penalty=float(config.repetition_penalty))
+                                            repetition_penalty=float(config.repetition_penalty), adapters=adapters)
                 print(tokenizer.decode(output_ids[0], skip_special_tokens=True).strip())
             else:
                 output_ids = model.generate(input_ids, images=image_tensor, do_sample=True, max_new_tokens=int(config.max_new_tokens), temperature=0.4,
                                             streamer=_Streamer(tokenizer), use_cache=True, stopping_criteria=[stopping_criteria], weights=weights,
-                                            sampler=config.sampler, repetition_penalty=float(config.repetition_penalty), seed=int(config.seed))
+                                            sampler=config.sampler, repetition_penalty=float(config.repetition_penalty), seed=int(config.seed),
+                                            adapters=adapters)
         outputs = tokenizer.decode(output_ids[0]).strip().split("<s>")[-1].strip()
         conv.messages[-1][-1] = outputs
         if config.debug:

@@ -359,6 +359,22 @@ int lhrs_repack_bf16_mfma(const void* W, long ldw, void* out, int N, int K, void
  * batches exceeding the LDS are split as in lhrs_gemv */
 int lhrs_gemv4(const void* codes, long ldc, const float* absmax, long lda, int fp4, const void* x, long ldx, int prologue, const void* norm_w,
                float eps, const void* residual, long ldr, void* y, long ldy, int B, int N, int K, int out_f32, void* stream);
+/* ---- decode with live adapters (peft lora.Linear.forward: y = W x + s B (A x), reached from lhrs/models/text_modal.py:133-151) at S_q = 1, for
+ * TextModal.generate(adapters="live"): the base GEMV of whatever weight format writes fp32 `acc` (out_f32, no residual), and two launches add
+ * the adapters on the same fp32 value before the single rounding - the arithmetic of lhrs_gemm_bf16_nt_lora.  No atomics: bit-reproducible.
+ * lora_down: tpart[i][b][j] (fp32 [nsl][B][R], nsl = lhrs_lora_down_splits(K, R); every element written) = sum over K-slice i of
+ *   pro(x)[b, k] A[j, k]; A bf16 [R, lda] = the stacked A of a fused group, R % 8 == 0, R <= 768; slice i = the 64-element chunks
+ *   [i * per, i * per + per) with per = ceil(K / 64 / nsl); prologue / norm_w / eps as lhrs_gemv (0 none, 1 RMSNorm, 2 SwiGLU over x = [B, 2K]);
+ *   1 <= B <= 16, K % 64 == 0.
+ * lora_up: t[b][j] = bf16(s * (tpart[0][b][j] + ... + tpart[nsl-1][b][j])) (ascending), y[b][n] = bf16(acc[b][n] + sum_{j in cols(n)} t[b][j]
+ *   Bw[n][j] + residual[b][n]) with cols(n) = [(n / fout) r, (n / fout) r + r): the one non-zero block of the block-diagonal row of Bw = Bfull
+ *   [N, ldb] bf16 - nothing else of the row is read.  r % 8 == 0, N % fout == 0, (N / fout) r <= R; r == R and fout == N: the dense form.
+ *   residual may be NULL; acc fp32 [B, ldacc], y bf16 [B, ldy]. */
+int lhrs_lora_down_splits(int K, int R); /* host helper, pure function of the shape: 1..16 K-slices */
+int lhrs_lora_down(const void* x, long ldx, int prologue, const void* norm_w, float eps, const void* A, long lda, float* tpart, int B, int R,
+                   int K, void* stream);
+int lhrs_lora_up(const float* acc, long ldacc, const float* tpart, int nsl, float s, const void* Bw, long ldb, int r, int fout,
+                 const void* residual, long ldr, void* y, long ldy, int B, int N, int R, void* stream);
 /* kernel A/B tests only: rows per wave / 1-KiB chunks per iteration of the batch-1 bf16 GEMV (0, 0 = the built-in shape rule) */
 int lhrs_gemv_set_tuning(int rows_per_wave, int chunks_per_iteration);
 int lhrs_quant_fp8_rows(const void* W, long ldw, void* W8, long ld8, float* scale, int N, int K, void* stream);

@@ -1186,6 +1186,73 @@ def gemv4(W4: Packed4, x, out, K, *, prologue=PRO_NONE, norm_w=None, eps=1e-5, r
     return out
 
 
+# --------------------------------------------------------------------------------------------- decode with live adapters
+LORA_DOWN_MAX_SLICES = 16
+LORA_DOWN_MAX_LDS = 160 * 1024 - 16   # bytes of staged activations a lora_down workgroup can hold (the CU's LDS less the kernel's static words)
+
+
+def lora_down_splits(K: int, R: int) -> int:
+    """K-slices `lora_down` cuts a [R, K] stacked A into (1..16; a pure function of the shape)."""
+    return int(_L().lhrs_lora_down_splits(int(K), int(R)))
+
+
+def lora_down_lds_bytes(B: int, K: int, R: int) -> int:
+    """bytes of LDS a `lora_down` workgroup stages: B rows of one K-slice in bf16 (the library rejects more than LORA_DOWN_MAX_LDS)"""
+    nsl = lora_down_splits(K, R)
+    return B * (-(-(K // 64) // nsl) * 64) * 2
+
+
+def lora_down(x, A, tpart, K, R=None, *, prologue=PRO_NONE, norm_w=None, eps=1e-5) -> int:
+    """tpart[i, b, j] = sum over K-slice i of pro(x)[b, k] * A[j, k] (fp32 [nsl, B, R], every element written) -> nsl.  A: bf16 [>= R, K] rows
+    (the stacked A of a fused group; R = the rows in use, default all); prologue / norm_w / eps as `gemv_fused`.  tpart: a contiguous fp32
+    buffer of at least nsl * B * R elements (a session sizes it for LORA_DOWN_MAX_SLICES)."""
+    _req(x, torch.bfloat16, "lora_down x")
+    _req(A, torch.bfloat16, "lora_down A")
+    _req(tpart, torch.float32, "lora_down tpart")
+    B = x.shape[0]
+    R = A.shape[0] if R is None else int(R)
+    if x.dim() != 2 or x.shape[1] != (2 * K if prologue == PRO_SWIGLU else K) or x.stride(1) != 1:
+        raise ValueError(f"lora_down: x {tuple(x.shape)} for K={K}, prologue {prologue} (SwiGLU reads [B, 2K]); rows must be dense")
+    if A.dim() != 2 or A.shape[0] < R or A.shape[1] != K or A.stride(1) != 1:
+        raise ValueError(f"lora_down: A {tuple(A.shape)}, expected at least ({R}, {K}) with dense rows")
+    if prologue == PRO_RMSNORM:
+        if norm_w is None or norm_w.numel() != K or not norm_w.is_contiguous():
+            raise ValueError(f"lora_down: the RMSNorm prologue needs a contiguous norm_w of {K} elements")
+        _req(norm_w, torch.bfloat16, "lora_down norm_w")
+    nsl = lora_down_splits(K, R)
+    if not tpart.is_contiguous() or tpart.numel() < nsl * B * R:
+        raise ValueError(f"lora_down: tpart holds {tpart.numel()} floats, {nsl} slices x {B} x {R} are written")
+    st = _L().lhrs_lora_down(x.data_ptr(), x.stride(0), prologue, _p(norm_w), float(eps), A.data_ptr(), A.stride(0), tpart.data_ptr(), B, R, K, _stream())
+    _lib.check(st, "lora_down")
+    return nsl
+
+
+def lora_up(acc, tpart, nsl, s, Bw, r, fout, out, *, residual=None, R=None):
+    """out[b, n] = bf16(acc[b, n] + sum_{j in cols(n)} t[b, j] * Bw[n, j] (+ residual[b, n])), t = bf16(s * sum_i tpart[i, b, :]) and
+    cols(n) = [(n // fout) * r, +r): only that block of the block-diagonal Bw = Bfull [N, >= R] is read (r == R and fout == N: dense).
+    acc: fp32 [B, N], the base product of the same linear (`gemv_fused` / `gemv4` / `gemv_fp8_mfma*` with out_f32 and no residual)."""
+    _req(acc, torch.float32, "lora_up acc")
+    _req(tpart, torch.float32, "lora_up tpart")
+    _req(Bw, torch.bfloat16, "lora_up Bw")
+    _req(out, torch.bfloat16, "lora_up out")
+    B, N = out.shape
+    R = (N // fout) * r if R is None else int(R)
+    if tuple(acc.shape) != (B, N) or acc.stride(1) != 1 or out.stride(1) != 1:
+        raise ValueError(f"lora_up: acc {tuple(acc.shape)} / out {tuple(out.shape)} must both be [B, N] with dense rows")
+    if Bw.dim() != 2 or Bw.shape[0] < N or Bw.shape[1] < (N // fout) * r or Bw.stride(1) != 1:
+        raise ValueError(f"lora_up: Bw {tuple(Bw.shape)} for N={N}, {N // fout} blocks of r={r} columns")
+    if not tpart.is_contiguous() or tpart.numel() < nsl * B * R:
+        raise ValueError(f"lora_up: tpart holds {tpart.numel()} floats, {nsl} slices x {B} x {R} are read")
+    if residual is not None:
+        _req(residual, torch.bfloat16, "lora_up residual")
+        if tuple(residual.shape) != (B, N) or residual.stride(1) != 1:
+            raise ValueError(f"lora_up: residual {tuple(residual.shape)}, expected ({B}, {N}) with dense rows")
+    st = _L().lhrs_lora_up(acc.data_ptr(), acc.stride(0), tpart.data_ptr(), int(nsl), float(s), Bw.data_ptr(), Bw.stride(0), int(r), int(fout),
+                           _p(residual), residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), B, N, R, _stream())
+    _lib.check(st, "lora_up")
+    return out
+
+
 class Int8Workspace:
     """Device scratch of the LLM.int8 activation side: outlier flags per input feature, the compacted outlier column list, meta = [columns
     found by the last call, that count rounded up to 64] and the persistent [N, KP + K] buffers of the dequantised outlier weight columns."""

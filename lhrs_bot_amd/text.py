@@ -727,12 +727,17 @@ class TextModal:
     __call__ = decode
 
     # ------------------------------------------------------------------ generate (KV cache)
-    def _layer_step(self, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None):
-        """One decoder layer over S_new new positions per sequence with `ctx` cached positions (prefill: ctx = 0)."""
+    def _layer_step(self, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None):
+        """One decoder layer over S_new new positions per sequence with `ctx` cached positions (prefill: ctx = 0).  li = the layer's index:
+        generate(adapters="live") - every adapted group runs its adapters through the training forward (`_lin` / `_gu_fwd`: gemm_nt_skinny, then
+        the base GEMM with the (T, Bfull) pair on its accumulators) on the bf16 base weights; the caller has switched dropout off."""
         d, H, hd, ff = self.d, self.heads, self.hd, self.ff
         M = x.shape[0]
         h = hk.rmsnorm_fwd(x, L["ln1_w"], self.eps)
-        qkv = hk.gemm_rope_fwd(h, L["qkv_w"], self.cos, self.sin, pos_mod=S_new, pos0=ctx, rope_cols=2 * d, head_dim=hd)
+        if li is None:
+            qkv = hk.gemm_rope_fwd(h, L["qkv_w"], self.cos, self.sin, pos_mod=S_new, pos0=ctx, rope_cols=2 * d, head_dim=hd)
+        else:
+            qkv = self._lin(li, "qkv", h, L["qkv_w"], rope=(S_new, ctx))
         kc, vc = cache
         row_b = d * 2
         for b in range(B):  # append the new K / V rows of sequence b at position ctx of its cache
@@ -741,6 +746,11 @@ class TextModal:
             hk.copy_2d(vc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + 2 * row_b, 3 * row_b, row_b, S_new)
         o = torch.empty((M, d), device=self.device, dtype=torch.bfloat16)
         hk.attn_fwd(qkv[:, :d], kc, vc, o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True, 1.0 / math.sqrt(hd), key_mask=kmask)
+        if li is not None:
+            x = self._lin(li, "o", o, L["o_w"], residual=x)
+            h = hk.rmsnorm_fwd(x, L["ln2_w"], self.eps, out=h)
+            _, act, _ = self._gu_fwd(li, h, L["gu_w"], None)
+            return self._lin(li, "down", act, L["down_w"], residual=x)
         x = hk.gemm_nt(o, L["o_w"], residual=x)
         h = hk.rmsnorm_fwd(x, L["ln2_w"], self.eps, out=h)
         act = hk.swiglu_fwd(hk.gemm_nt(h, L["gu_w"]), ff)
@@ -842,11 +852,17 @@ class TextModal:
         self.base8, self.base_int8 = True, False
         return self
 
-    def _decode_session(self, B, max_ctx, caches, max_new, weights="bf16", kmask=None):
+    def _decode_session(self, B, max_ctx, caches, max_new, weights="bf16", kmask=None, lora=None):
         """Static buffers + one captured hipGraph for the single-token step (batch <= 16): embedding gather, 32 x [RMSNorm,
         QKV GEMV, RoPE, KV append, attention over the cache, O GEMV + residual, RMSNorm, gate|up GEMV, SwiGLU, down GEMV +
         residual], final norm, lm_head GEMV -> fp32 logits.  Context length / positions live on the device
-        (decode_advance), so the graph is captured once and replayed for every token."""
+        (decode_advance), so the graph is captured once and replayed for every token.
+
+        lora = a LoraStore (generate(adapters="live")): a linear whose fused group carries adapters becomes three launches on the same stream -
+        `hk.lora_down` on the activation the base product sees, the GEMV of whatever weight format into the fp32 `s.acc` without its residual,
+        `hk.lora_up` into the linear's output with the residual: y = bf16(x W^T + (s x A^T) B^T + residual) on one fp32 value, what training's
+        `_lin` computes.  The session reads the store's bf16 shadow and `Bfull` in place (`LoraStore.refresh` rewrites their storage), so it
+        holds no copy of an adapter; un-adapted groups and lm_head launch exactly what they launch without a store."""
         dev, d, ff, H, hd, V = self.device, self.d, self.ff, self.heads, self.hd, self.vocab
         bf = torch.bfloat16
         s = types.SimpleNamespace()
@@ -896,7 +912,17 @@ class TextModal:
             s.x8 = (torch.zeros((B, d), device=dev, dtype=torch.uint8), torch.zeros(B, device=dev, dtype=torch.float32))
             s.a8 = (torch.zeros((B, ff), device=dev, dtype=torch.uint8), torch.zeros(B, device=dev, dtype=torch.float32))
 
-        def lin(w, sc, x_in, out, K, pro=hk.PRO_NONE, norm_w=None, residual=None, out_f32=False):
+        def staged(x_in, pro, norm_w):
+            """the batched path's materialised activation (RMSNorm / SwiGLU run once into s.hn / s.actb, the linear then has no prologue)"""
+            if batched and pro == hk.PRO_RMSNORM:
+                hk.rmsnorm_fwd(x_in, norm_w, self.eps, out=s.hn)
+                return s.hn, hk.PRO_NONE, None
+            if batched and pro == hk.PRO_SWIGLU:
+                hk.swiglu_fwd(x_in, ff, out=s.actb)
+                return s.actb, hk.PRO_NONE, norm_w
+            return x_in, pro, norm_w
+
+        def base(w, sc, x_in, out, K, pro=hk.PRO_NONE, norm_w=None, residual=None, out_f32=False):
             if fp8 and B <= 2:  # prologue + activation quantisation inside the GEMV: five launches per layer
                 hk.gemv_fp8_mfma_fused(w, sc, x_in, out, K, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
                 return
@@ -910,16 +936,37 @@ class TextModal:
                     q = hk.quant_fp8_rows(x_in, out=s.x8)
                 hk.gemv_fp8_mfma(w, sc, q[0], q[1], out, residual=residual, out_f32=out_f32)
                 return
-            if batched and pro == hk.PRO_RMSNORM:
-                hk.rmsnorm_fwd(x_in, norm_w, self.eps, out=s.hn)
-                x_in, pro, norm_w = s.hn, hk.PRO_NONE, None
-            elif batched and pro == hk.PRO_SWIGLU:
-                hk.swiglu_fwd(x_in, ff, out=s.actb)
-                x_in, pro = s.actb, hk.PRO_NONE
+            x_in, pro, norm_w = staged(x_in, pro, norm_w)
             if isinstance(w, hk.Packed4):
                 hk.gemv4(w, x_in, out, K, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
                 return
             hk.gemv_fused(w, x_in, out, K, wscale=sc, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
+
+        ad = {}   # (layer, group) -> (A [KP, in], Bfull [out_total, KP], R rows in use, r, fout) of the adapted groups
+        if lora is not None and lora.groups:
+            for gname, G in lora.groups.items():
+                nproj = len(G["projs"])
+                # blocks of r columns need 16-B lane loads; any other rank runs the dense form over the padded rows (their A rows and B columns are zero)
+                R, r_up, fo = (lora.r * nproj, lora.r, G["fout"]) if lora.r % 8 == 0 else (G["KP"], G["KP"], G["out_total"])
+                if R > 768:
+                    raise ValueError(f'adapters="live": group {gname!r} stacks {R} adapter rows, the decode kernels take at most 768 - use adapters="merged"')
+                if hk.lora_down_lds_bytes(B, G["fin"], R) > hk.LORA_DOWN_MAX_LDS:   # the rule of lhrs_lora_down, applied before anything is enqueued or captured
+                    raise ValueError(f'adapters="live": a K-slice of group {gname!r} (K = {G["fin"]}, {R} adapter rows) for {B} rows does not fit the LDS - '
+                                     'use adapters="merged"')
+                for li in range(len(self.p["layers"])):
+                    ad[(li, gname)] = (lora.view(lora.shadow, li, gname, "A"), lora.derived[(li, gname, "Bfull")], R, r_up, fo)
+            s.acc = torch.zeros((B, max(3 * d, 2 * ff)), device=dev, dtype=torch.float32)
+            s.tpart = torch.zeros(hk.LORA_DOWN_MAX_SLICES * B * max(a[2] for a in ad.values()), device=dev, dtype=torch.float32)
+
+        def lin(w, sc, x_in, out, K, pro=hk.PRO_NONE, norm_w=None, residual=None, out_f32=False, adapter=None):
+            if adapter is None:
+                return base(w, sc, x_in, out, K, pro, norm_w, residual, out_f32)
+            x_in, pro, norm_w = staged(x_in, pro, norm_w)   # once, for the adapter and the base alike (base() then finds no prologue left)
+            A, Bfull, R, r_up, fo = adapter
+            acc = s.acc[:, :out.shape[1]]
+            nsl = hk.lora_down(x_in, A, s.tpart, K, R, prologue=pro, norm_w=norm_w, eps=self.eps)
+            base(w, sc, x_in, acc, K, pro, norm_w, None, True)
+            hk.lora_up(acc, s.tpart, nsl, lora.s, Bfull, r_up, fo, out, residual=residual, R=R)
 
         # split-context attention (lhrs_decode_attn_split): 128-key slices, one workgroup each, so that a long context streams through
         # 32 * nsplit CUs; LHRS_DECODE_SPLIT=0 keeps the one-workgroup-per-head kernel (A/B runs)
@@ -934,8 +981,8 @@ class TextModal:
             hk.decode_advance(s.state, s.desc, s.pos, B, max_ctx, 1, self.cos, self.sin, cs)
             hk.gather_rows(self.p["embed"], s.tok32, out=s.x)
             x, x2 = s.x, s.x2
-            for L, (kc, vc) in zip(self.p["layers"], caches):
-                lin(*W(L, "qkv_w"), x, s.qkv, d, hk.PRO_RMSNORM, L["ln1_w"])
+            for li, (L, (kc, vc)) in enumerate(zip(self.p["layers"], caches)):
+                lin(*W(L, "qkv_w"), x, s.qkv, d, hk.PRO_RMSNORM, L["ln1_w"], adapter=ad.get((li, "qkv")))
                 if hd == 128 and nsplit > 1:  # RoPE + KV append + attention over the cache in one launch, context split over workgroups
                     hk.decode_attn_split(s.qkv, kc, vc, self.cos, self.sin, s.pos, s.o, B, H, hd, max_ctx, scale, nsplit, s.attn_part,
                                          s.attn_tickets, key_mask=kmask, cs=cs)
@@ -944,9 +991,9 @@ class TextModal:
                 else:
                     hk.rope_kv_append(s.qkv, kc, vc, self.cos, self.sin, s.pos, B, H, hd, max_ctx)
                     hk.attn_fwd(s.qkv[:, :d], kc, vc, s.o, None, s.desc, B, H, hd, 1, 1 << 30, 64, True, scale, key_mask=kmask)
-                lin(*W(L, "o_w"), s.o, x2, d, residual=x)
-                lin(*W(L, "gu_w"), x2, s.gu, d, hk.PRO_RMSNORM, L["ln2_w"])
-                lin(*W(L, "down_w"), s.gu, x, ff, hk.PRO_SWIGLU, residual=x2)
+                lin(*W(L, "o_w"), s.o, x2, d, residual=x, adapter=ad.get((li, "o")))
+                lin(*W(L, "gu_w"), x2, s.gu, d, hk.PRO_RMSNORM, L["ln2_w"], adapter=ad.get((li, "gu")))
+                lin(*W(L, "down_w"), s.gu, x, ff, hk.PRO_SWIGLU, residual=x2, adapter=ad.get((li, "down")))
             w, sc = (self.p["lm_head8p"], self.p["lm_head8s"]) if fp8 else (self.p["lm_headp"] if packed16 else self.p["lm_head"], None)
             lin(w, sc, x, s.logits, d, hk.PRO_RMSNORM, self.p["norm_w"], out_f32=True)
 
@@ -977,15 +1024,21 @@ class TextModal:
     def generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p="default",
                  top_k="default", max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id="default",
                  return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1,
-                 length_penalty=1.0, early_stopping=False, return_beam_scores=False, **_kw):
+                 length_penalty=1.0, early_stopping=False, return_beam_scores=False, adapters="merged", **_kw):
         """See `_generate`.  Two things happen here first: (1) `eos_token_id` defaults to the tokenizer's EOS, as HF `generate` stops on
-        the generation config's EOS (pass None to disable); (2) if LoRA adapters are attached and not merged, the call runs on merged
-        COPIES of the affected weights (`_lora_merged_layers`) and the base weights come back untouched.
+        the generation config's EOS (pass None to disable); (2) if LoRA adapters are attached and not merged, `adapters` says how they run:
+        "merged" (default) - on merged COPIES of the affected weights (`_lora_merged_layers`), the base weights come back untouched;
+        "live" - no copies: prefill and the batch > 16 steps run the training forward with dropout off, and the single-token step runs
+        `hk.lora_down` / `hk.lora_up` around the base GEMV of whatever `weights` streams (`_decode_session`), "4bit" included and "fp8" on the
+        e4m3 copies of the BASE weights; what it computes is x W^T + (s x A^T) B^T on one fp32 value, as training does, where "merged" rounds
+        W + s B A to bf16 first.  Without adapters "live" changes nothing.
 
         `weights`: what the single-token step streams - "bf16" (default, whatever the base), "fp8" (e4m3 copies on the block-scaled MFMA) or
         "4bit" (the codes and block statistics of `quantize_base(4)` through `hk.gemv4`; the decoder linears then compute what "bf16" computes
         on the dequantised weights up to the order of the fp32 sums; lm_head stays bf16).  "4bit" raises ValueError without the 4-bit base and
-        with un-merged adapters."""
+        with un-merged adapters unless `adapters="live"`."""
+        if adapters not in ("merged", "live"):
+            raise ValueError(f"adapters={adapters!r}: expected 'merged' or 'live'")
         if eos_token_id == "default":
             eos_token_id = getattr(self.tokenizer, "eos_token_id", None)
         # sampling defaults of the reference's callers: HF GenerationConfig top_k = 50 and the Llama-2 generation_config.json top_p = 0.9
@@ -1001,9 +1054,18 @@ class TextModal:
                   return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1))
         if self.lora is None:
             return self._generate(input_ids, **kw)
+        if adapters == "live":   # nothing is merged or swapped: the bf16 base weights serve prefill, `weights` picks the decode stream, dropout is off
+            lo = self.lora
+            saved = lo.train_mode, self.base8, self.base_int8
+            lo.train_mode, self.base8, self.base_int8 = False, False, False
+            try:
+                return self._generate(input_ids, live_lora=True, **kw)
+            finally:
+                lo.train_mode, self.base8, self.base_int8 = saved
         if weights == "4bit":
             raise ValueError('weights="4bit" with un-merged LoRA adapters: generate() then runs on merged 16-bit COPIES, which have no 4-bit form - '
-                             'call merge_lora() first (it re-quantises the merged weights, as peft does for a merged Linear4bit)')
+                             'call merge_lora() first (it re-quantises the merged weights, as peft does for a merged Linear4bit), or pass '
+                             'adapters="live" (the adapters then run next to the 4-bit codes)')
         base_layers, base8, base_i8 = self.p["layers"], self.base8, self.base_int8
         self.p["layers"], self.base8, self.base_int8 = self._lora_merged_layers(), False, False   # merged 16-bit copies: no 8-bit operands of them exist
         try:
@@ -1014,7 +1076,7 @@ class TextModal:
     def _generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p=None,
                   top_k=None, max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id=None,
                   return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1,
-                  length_penalty=1.0, early_stopping=False, return_beam_scores=False, num_return_sequences=1, **_kw):
+                  length_penalty=1.0, early_stopping=False, return_beam_scores=False, num_return_sequences=1, live_lora=False, **_kw):
         """TextModal.generate (text_modal.py:528-627): prefill over the spliced embeddings, then one token at a time with
         a KV cache; returns only the NEW token ids [B, n_new] (HF generate started from inputs_embeds).  Greedy
         (do_sample=False, the evaluation scripts' mode) runs entirely in HIP kernels; with do_sample=True the HIP-computed
@@ -1035,7 +1097,7 @@ class TextModal:
         if int(num_beams) != 1:
             return self._generate_beam(input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer,
                                        eos_token_id, return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty,
-                                       early_stopping, return_beam_scores, num_return_sequences)
+                                       early_stopping, return_beam_scores, num_return_sequences, live_lora)
         pen = float(repetition_penalty)
         device_pick = (sampler == "device" and do_sample) or pen != 1.0
         if streamer is not None and getattr(streamer, "skip_prompt", False):
@@ -1056,13 +1118,14 @@ class TextModal:
         caches = [(torch.empty((B * max_ctx, d), device=dev, dtype=torch.bfloat16), torch.empty((B * max_ctx, d), device=dev, dtype=torch.bfloat16))
                   for _ in range(len(self.p["layers"]))]
 
+        lora = self.lora if live_lora else None   # adapters="live": the store the session and the GEMM steps read
         s, seen, step_dev = None, None, None
         if device_pick:
             seed = int(torch.initial_seed() if seed is None else seed)
             if pen != 1.0:  # bitmap of the tokens generated so far in this call (HF started from inputs_embeds: the prompt is not in it)
                 seen = torch.zeros((B, (self.vocab + 31) // 32), device=dev, dtype=torch.int32)
             if B <= 16:  # the draw's step counter is the session's count of emitted tokens, on the device
-                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask)
+                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora)
                 s.state[0], s.state[1] = S0, 0
                 step_dev = s.state[1:2]
 
@@ -1080,8 +1143,8 @@ class TextModal:
         # ---- prefill (GEMM path) -> logits of the last prompt position -> first new token
         desc = hk.make_desc([(b * S0, S0, b * max_ctx, S0, S0, 0) for b in range(B)], dev)
         x = embeds.reshape(B * S0, d)
-        for L, cache in zip(self.p["layers"], caches):
-            x = self._layer_step(L, x, B, S0, 0, cache, desc, max_ctx, kmask)
+        for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
+            x = self._layer_step(L, x, B, S0, 0, cache, desc, max_ctx, kmask, li=li if lora is not None else None)
         hn = hk.rmsnorm_fwd(x.view(B, S0, d)[:, -1].contiguous(), self.p["norm_w"], self.eps)
         logits = hk.gemm_nt(hn, self.p["lm_head"], out_f32=True)  # [B, V] fp32 (HF: logits.float())
         all_logits = [logits.clone()] if return_logits else []
@@ -1104,7 +1167,7 @@ class TextModal:
         n_done = 1
         if B <= 16:
             if s is None:
-                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask)
+                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora)
                 s.state[0], s.state[1] = S0, 0
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream())
@@ -1148,8 +1211,8 @@ class TextModal:
             while not stop and n_done < max_new_tokens:
                 x = hk.gather_rows(self.p["embed"], out_ids[-1].clamp(0, self.vocab - 1).to(torch.int32))
                 desc = hk.make_desc([(b, 1, b * max_ctx, ctx + 1, ctx + 1, ctx) for b in range(B)], dev)
-                for L, cache in zip(self.p["layers"], caches):
-                    x = self._layer_step(L, x, B, 1, ctx, cache, desc, max_ctx, kmask)
+                for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
+                    x = self._layer_step(L, x, B, 1, ctx, cache, desc, max_ctx, kmask, li=li if lora is not None else None)
                 logits = hk.gemm_nt(hk.rmsnorm_fwd(x, self.p["norm_w"], self.eps), self.p["lm_head"], out_f32=True)
                 if return_logits:
                     all_logits.append(logits.clone())
@@ -1168,7 +1231,7 @@ class TextModal:
 
     def _generate_beam(self, input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer, eos_token_id,
                        return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty, early_stopping, return_beam_scores,
-                       num_return_sequences):
+                       num_return_sequences, live_lora=False):
         """Deterministic beam search, HF `generate(num_beams=nb, do_sample=False)` (generation/utils.py _beam_search; the web UI's
         answer_prepare kwargs): the prompt is prefilled ONCE per batch row into cache row b * nb and replicated to the row's other beams by
         `hk.kv_beam_reorder`; every further token is one linear single-stream graph of [model step over B * nb rows, beam_topk_rows, beam_step,
@@ -1205,7 +1268,8 @@ class TextModal:
             kmask_r = kmask.repeat_interleave(nb, 0).contiguous()
         caches = [(torch.empty((R * max_ctx, d), device=dev, dtype=torch.bfloat16), torch.empty((R * max_ctx, d), device=dev, dtype=torch.bfloat16))
                   for _ in range(len(self.p["layers"]))]
-        s = self._decode_session(R, max_ctx, caches, max_new_tokens, weights, kmask_r)
+        lora = self.lora if live_lora else None
+        s = self._decode_session(R, max_ctx, caches, max_new_tokens, weights, kmask_r, lora)
         s.state[0], s.state[1] = S0, 0
         st = hk.BeamState(B, nb, V, max_new_tokens, length_penalty, dev)
         table = hk.kv_cache_table(caches, dev)
@@ -1213,8 +1277,8 @@ class TextModal:
         # ---- prefill: sequence b into cache row b * nb (a cache "row" of nb * max_ctx positions), logits of the last prompt position
         desc = hk.make_desc([(b * S0, S0, b * nb * max_ctx, S0, S0, 0) for b in range(B)], dev)
         x = embeds.reshape(B * S0, d)
-        for L, cache in zip(self.p["layers"], caches):
-            x = self._layer_step(L, x, B, S0, 0, cache, desc, nb * max_ctx, kmask)
+        for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
+            x = self._layer_step(L, x, B, S0, 0, cache, desc, nb * max_ctx, kmask, li=li if lora is not None else None)
         hn = hk.rmsnorm_fwd(x.view(B, S0, d)[:, -1].contiguous(), self.p["norm_w"], self.eps)
         logits = hk.gemm_nt(hn, self.p["lm_head"], out_f32=True).repeat_interleave(nb, 0).contiguous()   # the row's beams all start from it
         all_logits = [logits] if return_logits else []

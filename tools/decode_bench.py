@@ -10,6 +10,12 @@
                                                                                  every repeat.  With `4bit` in the list the model is put on the
                                                                                  4-bit base (quantize_base(4, nf4, double_quant)) before the warm-up;
                                                                                  `bf16` then streams the dequantised weights: same bytes, same speed
+    python tools/decode_bench.py 256 bf16,4bit 1 --lora-r 8 --lora-targets q,k,v,o --adapters merged,live --repeats 3
+                                                                                 un-merged LoRA adapters (random, non-zero B): generate(adapters=...)
+                                                                                 modes alternate inside every repeat.  Each mode's FIRST call starts
+                                                                                 from a model without derived copies and is timed on its own (merged
+                                                                                 pays its merge and re-tiling there), with its peak allocated bytes;
+                                                                                 merged + 4bit does not exist and prints "n/a: raises"
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,6 +32,9 @@ ap.add_argument("--repeats", type=int, default=1, help="timed runs (one line eac
 ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--num-beams", type=int, default=1, help="> 1: mode `beam` (generate(num_beams=N)) alternates with mode `rows` (greedy at batch N x BATCH)")
 ap.add_argument("--beam-only", action="store_true", help="with --num-beams: mode `beam` alone (kernel traces)")
+ap.add_argument("--lora-r", type=int, default=0, help="> 0: attach un-merged LoRA adapters of this rank (alpha = 2 r, random A and B)")
+ap.add_argument("--lora-targets", default="all", help="q,k,v,o | all (every decoder linear)")
+ap.add_argument("--adapters", default="merged", help="merged | live | a comma list that alternates (generate(adapters=...); needs --lora-r)")
 a = ap.parse_args()
 new, B = a.new, a.batch
 weight_modes = a.weights.split(",")
@@ -38,6 +47,17 @@ assert all(m in ("off", "torch", "device", "beam", "rows") for m in modes), a.sa
 ids_rows, rgb_rows = ids.repeat(a.num_beams, 1), rgb.repeat(a.num_beams, 1, 1, 1)   # mode `rows`: the prompt N times
 if "4bit" in weight_modes:
     model.text.quantize_base(4, quant_type="nf4", double_quant=True)
+adapter_modes = a.adapters.split(",") if a.lora_r > 0 else [None]
+assert all(m in ("merged", "live", None) for m in adapter_modes), a.adapters
+if a.lora_r > 0:
+    targets = ("q", "k", "v", "o", "gate", "up", "down") if a.lora_targets == "all" else tuple(a.lora_targets.split(","))
+    lora = model.enable_lora(r=a.lora_r, alpha=2 * a.lora_r, targets=targets, seed=0)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    for l in range(a.layers):       # peft starts B at zero: give it values so that the adapters move the logits
+        for pr in targets:
+            A, Bm = lora.get_adapter(l, pr)
+            lora.set_adapter(l, pr, A, torch.randn(Bm.shape, device="cuda", generator=g) * 0.02)
+    lora.refresh()
 
 
 def token_bytes_4bit():
@@ -52,10 +72,12 @@ def token_bytes_4bit():
     return total
 
 
-def kwargs(mode, weights):
+def kwargs(mode, weights, adapters=None):
     # eos_token_id=None in EVERY mode (as bench.py --decode and cli_qa.py --synthetic-prompt time it): with an EOS the host synchronises on every
     # token and torch operators run between the graph replay and decode_emit, whoever picks the token
     kw = dict(do_sample=False, weights=weights, eos_token_id=None)
+    if adapters is not None:
+        kw.update(adapters=adapters)
     if mode == "beam":
         kw.update(num_beams=a.num_beams)
     elif mode not in ("off", "rows"):
@@ -69,20 +91,56 @@ def inputs(mode):
     return (ids_rows, rgb_rows) if mode == "rows" else (ids, rgb)
 
 
-runs = [(mode, weights) for mode in modes for weights in weight_modes]
-for mode, weights in runs:
-    model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=4, **kwargs(mode, weights))
+def drop_derived_copies():
+    """forget the merged weights and every derived decode copy (re-tiled bf16, e4m3 and their tiles, the packed 4-bit codes): the next call
+    builds what its mode needs.  The quantisation states of the 4-bit base (`q4`) and the int8 rows stay: they ARE the base, not copies of it."""
+    model.text._merged_cache = None
+    keep = ("q4", "i8", "i8s")
+    for L in model.text.p["layers"]:
+        for k in ("qkv_w", "o_w", "gu_w", "down_w"):
+            for suf in type(model.text).DERIVED_SUFFIXES:
+                if suf not in keep:
+                    L.pop(k + suf, None)
+    for k in ("lm_headp", "lm_head8", "lm_head8s", "lm_head8p"):
+        model.text.p.pop(k, None)
+    torch.cuda.empty_cache()
+
+
+runs = []
+for mode in modes:
+    for weights in weight_modes:
+        for ad in adapter_modes:
+            if ad == "merged" and weights == "4bit":
+                print(f"[{weights}, batch {B}, adapters merged] n/a: raises (merged 16-bit copies have no 4-bit form)", flush=True)
+                continue
+            runs.append((mode, weights, ad))
+for mode, weights, ad in runs:
+    if ad is not None:               # first call of an adapter mode, from a clean model: merge / re-tiling / capture cost and the peak footprint
+        drop_derived_copies()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+    model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=4, **kwargs(mode, weights, ad))
+    if ad is not None:
+        torch.cuda.synchronize()
+        print(f"[{weights}, batch {B}, adapters {ad}] first call (4 new tokens) {time.perf_counter() - t0:.3f}s, peak allocated "
+              f"{torch.cuda.max_memory_allocated() / 1e9:.2f} GB", flush=True)
+if len(adapter_modes) > 1:           # the alternating timed runs keep every mode's copies resident: rebuild them all once, untimed
+    for mode, weights, ad in runs:
+        model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=4, **kwargs(mode, weights, ad))
 roofline = {"fp8": "6.74 GB/token @ 8 TB/s = 1190 tok/s", "bf16": "13.5 GB/token @ 8 TB/s = 590 tok/s"}
 if "4bit" in weight_modes:
     gb = token_bytes_4bit() / 1e9
     roofline["4bit"] = f"{gb:.3g} GB/token @ 8 TB/s = {8000 / gb:.0f} tok/s"
 for _ in range(a.repeats):
-    for mode, weights in runs:
+    for mode, weights, ad in runs:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=new, **kwargs(mode, weights))
+        out = model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=new, **kwargs(mode, weights, ad))
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         n_new = out.shape[1]
         name = {"off": "greedy", "beam": f"beam search x{a.num_beams}", "rows": f"greedy, {out.shape[0]} rows"}.get(mode, f"sampled/{mode}")
+        if ad is not None:
+            name += f", adapters {ad}"
         print(f"[{weights}, batch {B}, {name}] {B}x{n_new} new tokens in {dt:.3f}s = {B*n_new/dt:.1f} tok/s (incl. ViT+pooler+prefill of {60-1+144} positions); HBM roofline " + roofline[weights] + " per sequence", flush=True)
