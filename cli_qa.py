@@ -7,7 +7,8 @@ flag-compatible (`-c Config/multi_modal_eval.yaml --model-path <FINAL.pt dir> --
 
 The prefill runs on the GEMM path, the per-token step is one captured hipGraph (lhrs_bot_amd/text.py `_decode_session`);
 `bits: 8` in the YAML (or `--opts bits 8`) streams e4m3 weights through the MFMA GEMV; `--decode-weights 4bit` with `bits: 4` streams
-the NF4 / FP4 codes of the 4-bit base (lhrs_gemv4).
+the NF4 / FP4 codes of the 4-bit base (lhrs_gemv4); `--decode-weights mxfp4` (any base) streams OCP MXFP4 copies on the FP4 MFMA
+(lhrs_gemv_mx4).
 
 Imports and call order follow /root/reference cli_qa.py:10-22, 84-193 over the `lhrs.*` surface.  Weights / tokenizer come from the paths
 in the YAML (`text.path`, `rgb_vision.vit_name`); when they are not on disk the towers are random-initialised and the word-hash
@@ -53,11 +54,13 @@ def parse_option(args=None):
     p.add_argument("--repetition-penalty", type=float, default=1.0, help="HF repetition_penalty over the generated tokens (the web UI uses 1.05)")
     p.add_argument("--num-beams", type=int, default=1, help="HF num_beams: > 1 answers by deterministic beam search on the device (no sampling, no token "
                                                             "stream: the answer is printed when the search ends); batch * num_beams <= 16")
-    p.add_argument("--decode-weights", default=None, choices=["bf16", "fp8", "4bit"],
+    p.add_argument("--decode-weights", default=None, choices=["bf16", "fp8", "4bit", "mxfp4"],
                    help="what the single-token step streams (default: fp8 iff `bits: 8`, else bf16); 4bit reads the NF4 / FP4 codes of the `bits: 4` "
                         "base directly and requires it; if the decoder is not on that base yet (an evaluation run has not been through "
                         "prepare_for_training) it is put there first with the YAML's quant_type / double_quant, so the prefill too reads "
-                        "the dequantised weights, as every product of the reference's Linear4bit does")
+                        "the dequantised weights, as every product of the reference's Linear4bit does; mxfp4 (any base, no YAML key) streams OCP MXFP4 "
+                        "copies of the decoder linears - e2m1 codes with one e8m0 scale per 32 weights, multiplied by the FP4 MFMA against e4m3 "
+                        "activations: lossy like fp8, lm_head and prefill stay bf16")
     p.add_argument("--adapters", default="merged", choices=["merged", "live"],
                    help="un-merged LoRA adapters (stage >= 1 with a TextLoRA/ loaded): merged = decode on merged 16-bit copies of the adapted weights; "
                         "live = no copies, the adapters run next to the base weights of whatever --decode-weights streams (4bit included)")

@@ -420,6 +420,26 @@ int lhrs_gemv_fp8_mfma_fused(const void* W8, long ldw, const float* wscale, cons
 /* w_packed != 0 in the two calls above: W8 is the copy this makes - the e4m3 rows re-tiled into the MFMA operand order
  * [N/16][K/128][2][64 lanes][16 B] (ceil(N/16)*16*K bytes), so that the decode weight stream is read as consecutive 1-KiB lines */
 int lhrs_repack_fp8_mfma(const void* W8, long ldw, void* out, int N, int K, void* stream);
+/* OCP MXFP4 decode weights (csrc/gemv_mx4.hip): e2m1 codes, uint8 [N, K/2] (element k in byte k/2, even k in the low nibble; a code is
+ * s m m m: sign, then an index into {0, .5, 1, 1.5, 2, 3, 4, 6}), and e8m0 block scales, uint8 [N, K/32] (2^(byte - 127) per 32 consecutive
+ * k).  Quantisation is the OCP MX v1.0 conversion: byte = clamp(floor(log2 max|v|) - 2 + 127, 0, 254) (127 and +0 codes for a zero
+ * block), elements rounded to the nearest level with ties to the even code, saturating at +-6.  K % 32 == 0; ldw in bf16, ldc / lds in
+ * bytes; pointers 16-byte aligned, ldc % 16 == 0. */
+int lhrs_quant_mx4_rows(const void* W, long ldw, void* codes, long ldc, void* scales, long lds, int N, int K, void* stream);
+int lhrs_dequant_mx4_rows(const void* codes, long ldc, const void* scales, long lds, void* W, long ldw, int N, int K, void* stream);
+/* row-major codes / scales -> the only form the GEMV reads (K % 128 == 0): codes_t [ceil(N/16)][K/128][64 lanes][16 B] - lane (r, g) of a
+ * step holds block 4 step + g of row 16 rg + r - and scales_t [ceil(N/16)][ceil(K/512)][64 lanes][4 B] - byte j of the lane's dword t is
+ * the scale of its block in step 4 t + j.  Rows past N are zero codes and byte 127; bytes of steps past K/128 are 127. */
+int lhrs_repack_mx4_mfma(const void* codes, long ldc, const void* scales, long lds, void* codes_t, void* scales_t, int N, int K, void* stream);
+/* y[B, N] = xscale[b] * (x8 . w^T) (+ residual), w = level * 2^(byte - 127) formed by v_mfma_scale_f32_16x16x128_f8f6f4 itself (FP4 A operand
+ * with its block scales, e4m3 B operand with unit scales); x8 / xscale as for lhrs_gemv_fp8_mfma; 1 <= B <= 16, K % 128 == 0; stored once,
+ * bf16 or (out_f32) fp32; no atomics */
+int lhrs_gemv_mx4(const void* codes_t, const void* scales_t, const void* x8, long ldx, const float* xscale,
+                  const void* residual, long ldr, void* y, long ldy, int B, int N, int K, int out_f32, void* stream);
+/* the same with bf16 activations and B <= 2: prologue (0 none, 1 RMSNorm, 2 SwiGLU over x = [B, 2K]) and the per-row e4m3 quantisation of x
+ * inside the kernel, as lhrs_gemv_fp8_mfma_fused does them */
+int lhrs_gemv_mx4_fused(const void* codes_t, const void* scales_t, const void* x, long ldx, int prologue, const void* norm_w, float eps,
+                        const void* residual, long ldr, void* y, long ldy, int B, int N, int K, int out_f32, void* stream);
 /* single-token attention for generate() (HF LlamaAttention with a KV cache at q_len = 1, reached from TextModal.generate,
  * lhrs/models/text_modal.py:586-627): RoPE of the new q / k row at device-resident position pos[b], append of (k, v) to the caches
  * [B * max_ctx, H*128] and attention over keys 0..pos[b] (optionally AND an HF attention_mask byte row), in ONE launch. */

@@ -1186,6 +1186,118 @@ def gemv4(W4: Packed4, x, out, K, *, prologue=PRO_NONE, norm_w=None, eps=1e-5, r
     return out
 
 
+# --------------------------------------------------------------------------------------------- decode from MXFP4 weights
+def quant_mx4_rows(W, out=None):
+    """bf16 [N, K] (K % 32 == 0) -> (codes uint8 [N, K/2], scales uint8 [N, K/32]): OCP MXFP4.  Element k of a row sits in byte k/2, even k in
+    the low nibble; a code is `s m m m` (sign, index into {0, .5, 1, 1.5, 2, 3, 4, 6}); a block of 32 consecutive k shares the e8m0 scale
+    2^(byte - 127) with byte = clamp(floor(log2 max|v|) - 2 + 127, 0, 254) (OCP MX v1.0; a zero block: 127 and +0 codes).  Elements round to
+    the nearest level, ties to the even code, saturating at +-6.  out = preallocated (codes, scales), rows may be strided."""
+    _req(W, torch.bfloat16, "quant_mx4_rows W")
+    N, K = W.shape
+    codes, scales = out if out is not None else (torch.empty((N, K // 2), device=W.device, dtype=torch.uint8),
+                                                 torch.empty((N, max(K // 32, 1)), device=W.device, dtype=torch.uint8))
+    if W.stride(1) != 1 or codes.stride(1) != 1 or scales.stride(1) != 1:
+        raise ValueError("quant_mx4_rows: rows must be dense")
+    _lib.check(_L().lhrs_quant_mx4_rows(W.data_ptr(), W.stride(0), codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), N, K,
+                                        _stream()), "quant_mx4_rows")
+    return codes, scales
+
+
+def dequant_mx4_rows(codes, scales, out=None):
+    """(codes [N, K/2], scales [N, K/32]) of `quant_mx4_rows` -> bf16 [N, K] = level * 2^(byte - 127), exact in bf16."""
+    _req(codes, torch.uint8, "dequant_mx4_rows codes")
+    _req(scales, torch.uint8, "dequant_mx4_rows scales")
+    N, K = codes.shape[0], codes.shape[1] * 2
+    if out is None:
+        out = torch.empty((N, K), device=codes.device, dtype=torch.bfloat16)
+    _req(out, torch.bfloat16, "dequant_mx4_rows out")
+    if tuple(out.shape) != (N, K) or tuple(scales.shape) != (N, K // 32) or out.stride(1) != 1 or codes.stride(1) != 1 or scales.stride(1) != 1:
+        raise ValueError(f"dequant_mx4_rows: codes {tuple(codes.shape)}, scales {tuple(scales.shape)}, out {tuple(out.shape)} with dense rows")
+    _lib.check(_L().lhrs_dequant_mx4_rows(codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), out.data_ptr(), out.stride(0), N, K,
+                                          _stream()), "dequant_mx4_rows")
+    return out
+
+
+class PackedMX4:
+    """MXFP4 weight [N, K] in the operand order of the decode GEMV (`repack_mx4_mfma`): `codes_t` uint8 [ceil(N/16), K/128, 64, 16] - lane
+    (r, g) of a 128-k step holds the 16 code bytes of block 4 step + g of row 16 rg + r - and `scales_t` uint8 [ceil(N/16), ceil(K/512), 64, 4] -
+    byte j of a lane's dword t is the scale of its block in step 4 t + j.  Rows past N: zero codes, scale byte 127."""
+
+    def __init__(self, codes_t, scales_t, N, K):
+        self.codes_t, self.scales_t, self.N, self.K = codes_t, scales_t, N, K
+        self.shape = (N, K)
+
+    def nbytes(self) -> int:
+        return self.codes_t.numel() + self.scales_t.numel()
+
+
+def repack_mx4_mfma(codes, scales, out=None) -> PackedMX4:
+    """row-major (codes, scales) -> PackedMX4 (K % 128 == 0); out = preallocated (codes_t, scales_t) of exactly the tiled sizes."""
+    _req(codes, torch.uint8, "repack_mx4_mfma codes")
+    _req(scales, torch.uint8, "repack_mx4_mfma scales")
+    N, K = codes.shape[0], codes.shape[1] * 2
+    if tuple(scales.shape) != (N, K // 32) or codes.stride(1) != 1 or scales.stride(1) != 1:
+        raise ValueError(f"repack_mx4_mfma: codes {tuple(codes.shape)} / scales {tuple(scales.shape)}: expected [N, K/2] and [N, K/32] with dense rows")
+    G, S = (N + 15) // 16, K // 128
+    if out is None:
+        out = (torch.empty((G, S, 64, 16), device=codes.device, dtype=torch.uint8), torch.empty((G, (S + 3) // 4, 64, 4), device=codes.device, dtype=torch.uint8))
+    ct, st = out
+    if K % 128 == 0 and (ct.numel() != G * S * 1024 or st.numel() != G * ((S + 3) // 4) * 256 or not ct.is_contiguous() or not st.is_contiguous()):
+        raise ValueError(f"repack_mx4_mfma: out of {ct.numel()} + {st.numel()} bytes for N={N}, K={K}")
+    _lib.check(_L().lhrs_repack_mx4_mfma(codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), ct.data_ptr(), st.data_ptr(), N, K,
+                                         _stream()), "repack_mx4_mfma")
+    return PackedMX4(ct, st, N, K)
+
+
+def _mx4_out(what, W, B, out, residual, out_f32):
+    _req(W.codes_t, torch.uint8, what + " codes_t")
+    _req(W.scales_t, torch.uint8, what + " scales_t")
+    _req(out, torch.float32 if out_f32 else torch.bfloat16, what + " out")
+    G, S = (W.N + 15) // 16, W.K // 128
+    if W.K % 128 == 0 and (W.codes_t.numel() != G * S * 1024 or W.scales_t.numel() != G * ((S + 3) // 4) * 256):
+        raise ValueError(f"{what}: the tiled buffers do not belong to a weight of shape {W.shape}")
+    if tuple(out.shape) != (B, W.N) or out.stride(1) != 1:
+        raise ValueError(f"{what}: out {tuple(out.shape)}, expected ({B}, {W.N}) with dense rows")
+    if residual is not None:
+        _req(residual, torch.bfloat16, what + " residual")
+        if tuple(residual.shape) != (B, W.N) or residual.stride(1) != 1:
+            raise ValueError(f"{what}: residual {tuple(residual.shape)}, expected ({B}, {W.N}) with dense rows")
+
+
+def gemv_mx4(W: PackedMX4, x8, xscale, out, *, residual=None, out_f32=False):
+    """out[B, N] = xscale[:, None] * (x8 @ w^T) (+ residual), w = the MXFP4 weight, dequantised by the block-scaled MFMA itself; x8 / xscale are
+    the per-row e4m3 activations of `quant_fp8_rows` / `rmsnorm_fwd_q` / `swiglu_fwd_q`.  1 <= B <= 16, K % 128 == 0."""
+    _req(x8, torch.uint8, "gemv_mx4 x8")
+    _req(xscale, torch.float32, "gemv_mx4 xscale")
+    B, K = x8.shape
+    if K != W.K or x8.stride(1) != 1 or xscale.numel() < B:
+        raise ValueError(f"gemv_mx4: x8 {tuple(x8.shape)} / xscale {tuple(xscale.shape)} for a weight of shape {W.shape}; rows must be dense")
+    _mx4_out("gemv_mx4", W, B, out, residual, out_f32)
+    st = _L().lhrs_gemv_mx4(W.codes_t.data_ptr(), W.scales_t.data_ptr(), x8.data_ptr(), x8.stride(0), xscale.data_ptr(), _p(residual),
+                            residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), B, W.N, K, int(out_f32), _stream())
+    _lib.check(st, "gemv_mx4")
+    return out
+
+
+def gemv_mx4_fused(W: PackedMX4, x, out, K, *, prologue=PRO_NONE, norm_w=None, eps=1e-5, residual=None, out_f32=False):
+    """batch <= 2: out = xscale * (e4m3(pro(x)) @ w^T) (+ residual), prologue and per-row activation quantisation inside the kernel, as in
+    `gemv_fp8_mfma_fused`."""
+    _req(x, torch.bfloat16, "gemv_mx4_fused x")
+    B = x.shape[0]
+    if K != W.K or x.dim() != 2 or x.shape[1] != (2 * K if prologue == PRO_SWIGLU else K) or x.stride(1) != 1:
+        raise ValueError(f"gemv_mx4_fused: x {tuple(x.shape)} for a weight of shape {W.shape}, prologue {prologue} (SwiGLU reads [B, 2K]); rows must be dense")
+    if prologue == PRO_RMSNORM:
+        if norm_w is None or norm_w.numel() != K or not norm_w.is_contiguous():
+            raise ValueError(f"gemv_mx4_fused: the RMSNorm prologue needs a contiguous norm_w of {K} elements")
+        _req(norm_w, torch.bfloat16, "gemv_mx4_fused norm_w")
+    _mx4_out("gemv_mx4_fused", W, B, out, residual, out_f32)
+    st = _L().lhrs_gemv_mx4_fused(W.codes_t.data_ptr(), W.scales_t.data_ptr(), x.data_ptr(), x.stride(0), prologue, _p(norm_w), float(eps),
+                                  _p(residual), residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), B, W.N, K,
+                                  int(out_f32), _stream())
+    _lib.check(st, "gemv_mx4_fused")
+    return out
+
+
 # --------------------------------------------------------------------------------------------- decode with live adapters
 LORA_DOWN_MAX_SLICES = 16
 LORA_DOWN_MAX_LDS = 160 * 1024 - 16   # bytes of staged activations a lora_down workgroup can hold (the CU's LDS less the kernel's static words)

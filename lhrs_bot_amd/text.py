@@ -277,7 +277,7 @@ class TextModal:
             self.quantize_base(4, quant_type=base4[0], double_quant=base4[1])   # peft re-quantises a merged Linear4bit the same way
 
     _W4_PARTS = {"qkv_w": 3, "o_w": 1, "gu_w": 2, "down_w": 1}   # reference Linears per fused weight (row-concatenated): 4-bit statistics are per Linear
-    DERIVED_SUFFIXES = ("p", "8", "8s", "8p", "i8", "i8s", "q4", "4p")   # decode re-tilings and e4m3 copies of a weight `<name>` / `<name>T`, rebuilt lazily from it
+    DERIVED_SUFFIXES = ("p", "8", "8s", "8p", "i8", "i8s", "q4", "4p", "mx4")   # decode re-tilings and e4m3 copies of a weight `<name>` / `<name>T`, rebuilt lazily from it
 
     def _drop_derived(self, L) -> None:
         """Forget every tensor that was computed FROM a decoder weight of layer dict `L` (decode re-tilings, e4m3 copies): after the weight
@@ -792,6 +792,17 @@ class TextModal:
             for k in self._W4_PARTS:
                 L[k + "4p"] = hk.pack4_decode(L[k + "q4"], *L[k].shape)
 
+    def pack_mx4_decode(self):
+        """Decode-only MXFP4 form of the decoder linears (`weights="mxfp4"`): whatever bf16 weight the decoder currently holds is quantised to
+        OCP MXFP4 (`hk.quant_mx4_rows`: e2m1 codes, one e8m0 scale per 32 consecutive k) and re-tiled into the operand order of `hk.gemv_mx4`;
+        only the tiled pair stays, under `L[name + "mx4"]` (+3.5 GB at full depth; the row-major temporaries of a weight are freed before the
+        next one is made).  Lossy, like `quantize_fp8`.  lm_head has no MXFP4 form."""
+        for L in self.p["layers"]:
+            for k in ("qkv_w", "o_w", "gu_w", "down_w"):
+                codes, scales = hk.quant_mx4_rows(L[k])
+                L[k + "mx4"] = hk.repack_mx4_mfma(codes, scales)
+                del codes, scales
+
     def quantize_base(self, bits: int = 8, scheme: str = "e4m3", quant_type: str = "nf4", double_quant: bool = True):
         """`bits: 8` of Config/multi_modal_stage{2,3}.yaml (text_modal.py:91-131: the reference loads the frozen LLaMA through bitsandbytes
         LLM.int8 for stages 2/3; lm_head stays 16-bit there and here).  Two schemes:
@@ -880,9 +891,9 @@ class TextModal:
         s.pos = torch.zeros(B, device=dev, dtype=torch.int32)
         scale = 1.0 / math.sqrt(hd)
 
-        if weights not in ("bf16", "fp8", "4bit"):
-            raise ValueError(f"weights={weights!r}: expected 'bf16', 'fp8' or '4bit'")
-        fp8, w4 = weights == "fp8", weights == "4bit"
+        if weights not in ("bf16", "fp8", "4bit", "mxfp4"):
+            raise ValueError(f"weights={weights!r}: expected 'bf16', 'fp8', '4bit' or 'mxfp4'")
+        fp8, w4, mx4 = weights == "fp8", weights == "4bit", weights == "mxfp4"
         if fp8 and "qkv_w8p" not in self.p["layers"][0]:
             self.pack_fp8_decode()
         if w4:  # the decoder linears stream the 4-bit codes (hk.gemv4); lm_head is not quantised in the reference and stays bf16
@@ -890,9 +901,14 @@ class TextModal:
                 raise ValueError('weights="4bit" needs the 4-bit base: quantize_base(4, quant_type, double_quant) (YAML `bits: 4`)')
             if "qkv_w4p" not in self.p["layers"][0]:
                 self.pack4_decode()
+        if mx4:  # the decoder linears stream MXFP4 codes + block scales (hk.gemv_mx4) against the e4m3 activations of the fp8 mode; lm_head stays bf16
+            if d % 128 or ff % 128:
+                raise ValueError(f'weights="mxfp4" needs hidden sizes that are multiples of 128 (the MFMA step), got {d} and {ff}')
+            if "qkv_wmx4" not in self.p["layers"][0]:
+                self.pack_mx4_decode()
 
         packed16 = not fp8 and B >= 2 and d % 128 == 0 and ff % 128 == 0  # batched bf16: the MFMA GEMV on re-tiled weights
-        if packed16 and w4:  # lm_head alone: pack_bf16_decode() would add 13.5 GB of re-tiled decoder weights that this mode never reads
+        if packed16 and (w4 or mx4):  # lm_head alone: pack_bf16_decode() would add 13.5 GB of re-tiled decoder weights that this mode never reads
             if "lm_headp" not in self.p:
                 self.p["lm_headp"] = hk.repack_bf16_mfma(self.p["lm_head"])
         elif packed16 and "qkv_wp" not in self.p["layers"][0]:
@@ -901,6 +917,8 @@ class TextModal:
         def W(L, name):  # (weight, per-row scale or None)
             if w4:
                 return L[name + "4p"], None
+            if mx4:
+                return L[name + "mx4"], None
             return (L[name + "8p"], L[name + "8s"]) if fp8 else (L[name + "p"] if packed16 else L[name], None)
 
         # the MFMA weight streams (bf16 and 4-bit alike) read x from L2 with prologue 0: norm / SwiGLU run once, not once per block (pays from batch 4)
@@ -908,7 +926,7 @@ class TextModal:
         if batched:
             s.hn = torch.zeros((B, d), device=dev, dtype=bf)
             s.actb = torch.zeros((B, ff), device=dev, dtype=bf)
-        if fp8:  # e4m3 weights AND activations on the block-scaled MFMA: static e4m3 operand buffers (graph capture: no allocation)
+        if fp8 or mx4:  # e4m3 activations on the block-scaled MFMA: static e4m3 operand buffers (graph capture: no allocation)
             s.x8 = (torch.zeros((B, d), device=dev, dtype=torch.uint8), torch.zeros(B, device=dev, dtype=torch.float32))
             s.a8 = (torch.zeros((B, ff), device=dev, dtype=torch.uint8), torch.zeros(B, device=dev, dtype=torch.float32))
 
@@ -935,6 +953,19 @@ class TextModal:
                 else:
                     q = hk.quant_fp8_rows(x_in, out=s.x8)
                 hk.gemv_fp8_mfma(w, sc, q[0], q[1], out, residual=residual, out_f32=out_f32)
+                return
+            if isinstance(w, hk.PackedMX4):   # as the fp8 branch: fused up to batch 2, else the quantising producers + the x8 form
+                if B <= 2:
+                    hk.gemv_mx4_fused(w, x_in, out, K, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
+                    return
+                if pro == hk.PRO_RMSNORM:
+                    _, q = hk.rmsnorm_fwd_q(x_in, norm_w, self.eps, want_bf16=False, q_out=s.x8)
+                elif pro == hk.PRO_SWIGLU:
+                    _, a8, sa = hk.swiglu_fwd_q(x_in, ff, q_out=s.a8)
+                    q = (a8, sa)
+                else:
+                    q = hk.quant_fp8_rows(x_in, out=s.x8 if K == d else s.a8)   # K = ff: the materialised SwiGLU of the batched live-adapter path
+                hk.gemv_mx4(w, q[0], q[1], out, residual=residual, out_f32=out_f32)
                 return
             x_in, pro, norm_w = staged(x_in, pro, norm_w)
             if isinstance(w, hk.Packed4):
@@ -1036,7 +1067,11 @@ class TextModal:
         `weights`: what the single-token step streams - "bf16" (default, whatever the base), "fp8" (e4m3 copies on the block-scaled MFMA) or
         "4bit" (the codes and block statistics of `quantize_base(4)` through `hk.gemv4`; the decoder linears then compute what "bf16" computes
         on the dequantised weights up to the order of the fp32 sums; lm_head stays bf16).  "4bit" raises ValueError without the 4-bit base and
-        with un-merged adapters unless `adapters="live"`."""
+        with un-merged adapters unless `adapters="live"`.
+        "mxfp4" - on any base: the decoder linears stream OCP MXFP4 copies (e2m1 codes + one e8m0 scale per 32 k, 0.53 B per weight, made by
+        `pack_mx4_decode` from whatever bf16 weights the decoder holds at the first call - merged copies included) against per-row e4m3
+        activations, dequantised and multiplied by the block-scaled MFMA itself (`hk.gemv_mx4`).  Lossy like "fp8" (the weights are rounded to
+        4 bits); lm_head stays bf16, and the prefill stays on the bf16 GEMMs in every mode."""
         if adapters not in ("merged", "live"):
             raise ValueError(f"adapters={adapters!r}: expected 'merged' or 'live'")
         if eos_token_id == "default":

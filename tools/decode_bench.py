@@ -10,6 +10,8 @@
                                                                                  every repeat.  With `4bit` in the list the model is put on the
                                                                                  4-bit base (quantize_base(4, nf4, double_quant)) before the warm-up;
                                                                                  `bf16` then streams the dequantised weights: same bytes, same speed
+    python tools/decode_bench.py 256 bf16,fp8,mxfp4 1 --repeats 3                the same with the MXFP4 decode copies (any base; generate builds them
+                                                                                 at the warm-up call)
     python tools/decode_bench.py 256 bf16,4bit 1 --lora-r 8 --lora-targets q,k,v,o --adapters merged,live --repeats 3
                                                                                  un-merged LoRA adapters (random, non-zero B): generate(adapters=...)
                                                                                  modes alternate inside every repeat.  Each mode's FIRST call starts
@@ -38,7 +40,7 @@ ap.add_argument("--adapters", default="merged", help="merged | live | a comma li
 a = ap.parse_args()
 new, B = a.new, a.batch
 weight_modes = a.weights.split(",")
-assert all(w in ("bf16", "fp8", "4bit") for w in weight_modes), a.weights
+assert all(w in ("bf16", "fp8", "4bit", "mxfp4") for w in weight_modes), a.weights
 model = UniBind(("rgb", "text"), None, device="cuda", llama_layers=a.layers).init_random(seed=0).eval()
 ids = torch.randint(3, 32000, (B, 60)); ids[:, 0] = 1; ids[:, 1] = -200
 rgb = torch.randn(B, 3, 224, 224)
@@ -69,6 +71,16 @@ def token_bytes_4bit():
     for L in model.text.p["layers"]:
         for k in ("qkv_w", "o_w", "gu_w", "down_w"):
             total += nbytes(L[k + "4p"].codes) + nbytes(L[k + "4p"].absmax)
+    return total
+
+
+def token_bytes_mxfp4():
+    """bytes of weights one `mxfp4` token streams, from the tensors generate() reads: the tiled codes and block scales (padding rows included)
+    of every decoder linear, and the bf16 lm_head"""
+    total = model.text.p["lm_head"].numel() * model.text.p["lm_head"].element_size()
+    for L in model.text.p["layers"]:
+        for k in ("qkv_w", "o_w", "gu_w", "down_w"):
+            total += L[k + "mx4"].nbytes()
     return total
 
 
@@ -132,6 +144,10 @@ roofline = {"fp8": "6.74 GB/token @ 8 TB/s = 1190 tok/s", "bf16": "13.5 GB/token
 if "4bit" in weight_modes:
     gb = token_bytes_4bit() / 1e9
     roofline["4bit"] = f"{gb:.3g} GB/token @ 8 TB/s = {8000 / gb:.0f} tok/s"
+if "mxfp4" in weight_modes and "qkv_wmx4" in model.text.p["layers"][0]:   # with adapters="merged" the copies hang on the merged layers instead
+    gb = token_bytes_mxfp4() / 1e9
+    roofline["mxfp4"] = f"{gb:.3g} GB/token @ 8 TB/s = {8000 / gb:.0f} tok/s"
+roofline.setdefault("mxfp4", "n/a (the MXFP4 copies belong to the merged layers)")
 for _ in range(a.repeats):
     for mode, weights, ad in runs:
         torch.cuda.synchronize()
