@@ -64,6 +64,9 @@ def parse_option(args=None):
     p.add_argument("--adapters", default="merged", choices=["merged", "live"],
                    help="un-merged LoRA adapters (stage >= 1 with a TextLoRA/ loaded): merged = decode on merged 16-bit copies of the adapted weights; "
                         "live = no copies, the adapters run next to the base weights of whatever --decode-weights streams (4bit included)")
+    p.add_argument("--kv-cache", default="bf16", choices=["bf16", "fp8"],
+                   help="KV cache of the decode step: bf16, or fp8 = e4m3 codes with one e8m0 scale byte per head row (half the cache memory and "
+                        "half the cache stream; the prompt itself is attended in bf16, so the first token is the bf16 one); batch x beams <= 16")
     p.add_argument("--length-penalty", type=float, default=1.0, help="HF length_penalty of the beam search: hypotheses score sum(log p) / length ** penalty")
     cfg = ConfigDict(p.parse_args(wandb=True, args=args))
     opts = cfg.get("opts") or []
@@ -121,6 +124,7 @@ def main(config):
     bits = int(config.get("bits", 16) or 16)
     weights = config.get("decode_weights") or ("fp8" if bits == 8 else "bf16")
     adapters = str(config.get("adapters") or "merged")
+    kv_cache = str(config.get("kv_cache") or "bf16")
     if weights == "4bit":
         if bits != 4:
             raise ValueError("--decode-weights 4bit requires `bits: 4` in the YAML (or --opts bits 4)")
@@ -143,7 +147,7 @@ def main(config):
         ids = torch.randint(3, 32000, (1, T), generator=g)
         ids[0, 0], ids[0, 1] = 1, IMAGE_TOKEN_INDEX
         kw = dict(images=image_tensor, do_sample=False, use_cache=True, weights=weights, eos_token_id=None, num_beams=int(config.num_beams),
-                  length_penalty=float(config.length_penalty), adapters=adapters)
+                  length_penalty=float(config.length_penalty), adapters=adapters, kv_cache=kv_cache)
         model.generate(ids, max_new_tokens=4, **kw)  # graph capture + allocator warm-up
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -179,13 +183,13 @@ def main(config):
             if int(config.num_beams) > 1:   # beam search stops on the tokenizer's EOS, on the device: no streamer, no host stopping criteria
                 output_ids = model.generate(input_ids, images=image_tensor, do_sample=False, max_new_tokens=int(config.max_new_tokens), use_cache=True,
                                             weights=weights, num_beams=int(config.num_beams), length_penalty=float(config.length_penalty),
-                                            repetition_penalty=float(config.repetition_penalty), adapters=adapters)
+                                            repetition_penalty=float(config.repetition_penalty), adapters=adapters, kv_cache=kv_cache)
                 print(tokenizer.decode(output_ids[0], skip_special_tokens=True).strip())
             else:
                 output_ids = model.generate(input_ids, images=image_tensor, do_sample=True, max_new_tokens=int(config.max_new_tokens), temperature=0.4,
                                             streamer=_Streamer(tokenizer), use_cache=True, stopping_criteria=[stopping_criteria], weights=weights,
                                             sampler=config.sampler, repetition_penalty=float(config.repetition_penalty), seed=int(config.seed),
-                                            adapters=adapters)
+                                            adapters=adapters, kv_cache=kv_cache)
         outputs = tokenizer.decode(output_ids[0]).strip().split("<s>")[-1].strip()
         conv.messages[-1][-1] = outputs
         if config.debug:

@@ -454,6 +454,21 @@ int lhrs_decode_attn(const void* qkv, long ld, void* kcache, void* vcache, const
 int lhrs_decode_attn_split(const void* qkv, long ld, void* kcache, void* vcache, const float* cos_t, const float* sin_t,
                            const int* pos, const unsigned char* key_mask, long ld_mask, void* out, long ldo, int B, int H, int D,
                            int max_ctx, float scale, int nsplit, float* part, int* tickets, const float* cs, void* stream);
+/* ---- the 8-bit KV cache "kv8" (csrc/decode_kv8.hip; TextModal.generate(kv_cache="fp8")): one cache position of one head = 128 values
+ * (keys after RoPE, already rounded to bf16) -> 128 OCP e4m3fn codes + one e8m0 scale byte.  m = max|v| of the 128: m == 0 -> byte 127 and
+ * +0 codes; else e = floor(log2 m) - 8, raised by one if m > 448 * 2^e, byte = clamp(e + 127, 0, 254), code = RNE_e4m3(v / 2^e): nothing
+ * saturates, no code is a NaN.  Per layer and per K / V, position-major like the bf16 caches: codes uint8 [rows * max_ctx][H * 128], scales
+ * uint8 [rows * max_ctx][H].
+ * kv8_quant_rows: src = bf16 rows [n][H * 128], row stride ld elements (ld % 8 == 0; the K or V column block of a qkv buffer in place) ->
+ * codes and scale bytes of the cache rows row0 .. row0 + n - 1. */
+int lhrs_kv8_quant_rows(const void* src, long ld, void* codes, void* scales, long row0, int n, int H, void* stream);
+/* lhrs_decode_attn_split on the kv8 caches, nsplit 1..16 (1: no exchange; part / tickets may then be NULL): RoPE of the new q / k row,
+ * quantisation of the new K and V head rows, their append (codes and scale byte) at pos[b] and attention over keys 0..pos[b] in ONE launch.
+ * The new token attends to the dequantised row it has just written, so the output is a function of the cache bytes alone; rows past the
+ * context and masked keys never reach the sums, whatever bytes they hold.  part / tickets / cs / key_mask as lhrs_decode_attn_split. */
+int lhrs_decode_attn_kv8(const void* qkv, long ld, void* kcodes, void* vcodes, void* kscales, void* vscales, const float* cos_t,
+                         const float* sin_t, const int* pos, const unsigned char* key_mask, long ld_mask, void* out, long ldo, int B, int H,
+                         int D, int max_ctx, float scale, int nsplit, float* part, int* tickets, const float* cs, void* stream);
 /* ---- data boundary: the image transform of the reference -------------------------------------------
  * CLIPImageProcessor.preprocess as built by build_vlp_transform (lhrs/Dataset/build_transform.py:43-45) for one decoded RGB image:
  * img = uint8 [H][W][3] on the device (row_stride bytes per row) -> out = float32 [3][224][224].  Bit-exact with Pillow's BICUBIC

@@ -932,6 +932,36 @@ def decode_attn_split(qkv, kc, vc, cos_t, sin_t, pos, out, B, H, D, max_ctx, sca
     return out
 
 
+def kv8_quant_rows(src, codes, scales, row0, H):
+    """lhrs_kv8_quant_rows: bf16 rows src [n, H * 128] (any row stride: a column block of a qkv buffer in place) -> the codes and scale
+    bytes of the cache rows row0 .. row0 + n - 1"""
+    _req(src, torch.bfloat16, "src")
+    _req(codes, torch.uint8, "codes")
+    _req(scales, torch.uint8, "scales")
+    n = src.shape[0]
+    assert src.shape[1] == H * 128 and src.stride(1) == 1 and codes.is_contiguous() and scales.is_contiguous()
+    assert codes.shape[1] == H * 128 and scales.shape[1] == H and 0 <= row0 and row0 + n <= codes.shape[0] and codes.shape[0] == scales.shape[0]
+    _lib.check(_L().lhrs_kv8_quant_rows(src.data_ptr(), src.stride(0), codes.data_ptr(), scales.data_ptr(), int(row0), n, H, _stream()),
+               "kv8_quant_rows")
+
+
+def decode_attn_kv8(qkv, kc8, vc8, ks, vs, cos_t, sin_t, pos, out, B, H, D, max_ctx, scale, nsplit=1, part=None, tickets=None, key_mask=None,
+                    cs=None):
+    """decode_attn / decode_attn_split on the kv8 caches (lhrs_decode_attn_kv8): kc8 / vc8 uint8 [B * max_ctx, H * 128], ks / vs uint8
+    [B * max_ctx, H]; nsplit > 1 needs part fp32 [B, H, nsplit, 132] and tickets int32 [B, H] (zero before the first call)."""
+    for t, name in ((kc8, "kc8"), (vc8, "vc8"), (ks, "ks"), (vs, "vs")):
+        _req(t, torch.uint8, name)
+        assert t.is_contiguous() and t.shape[0] >= B * max_ctx and t.shape[1] == (H * D if t is kc8 or t is vc8 else H), name
+    if nsplit > 1:
+        assert part.dtype == torch.float32 and part.numel() >= B * H * nsplit * 132 and tickets.dtype == torch.int32 and tickets.numel() >= B * H
+    st = _L().lhrs_decode_attn_kv8(qkv.data_ptr(), qkv.stride(0), kc8.data_ptr(), vc8.data_ptr(), ks.data_ptr(), vs.data_ptr(), cos_t.data_ptr(),
+                                   sin_t.data_ptr(), pos.data_ptr(), _p(key_mask), key_mask.stride(0) if key_mask is not None else 0,
+                                   out.data_ptr(), out.stride(0), B, H, D, max_ctx, float(scale), int(nsplit), _p(part), _p(tickets), _p(cs),
+                                   _stream())
+    _lib.check(st, "decode_attn_kv8")
+    return out
+
+
 def decode_advance(state, desc, pos, B, max_ctx, inc=1, cos_t=None, sin_t=None, cs=None):
     """cs (float32 [B, 128]) with the tables: also leave the cos | sin rows of the new position there (lhrs_decode_advance_cs)"""
     if cs is not None:

@@ -738,14 +738,26 @@ class TextModal:
             qkv = hk.gemm_rope_fwd(h, L["qkv_w"], self.cos, self.sin, pos_mod=S_new, pos0=ctx, rope_cols=2 * d, head_dim=hd)
         else:
             qkv = self._lin(li, "qkv", h, L["qkv_w"], rope=(S_new, ctx))
-        kc, vc = cache
-        row_b = d * 2
-        for b in range(B):  # append the new K / V rows of sequence b at position ctx of its cache
-            src = qkv.data_ptr() + b * S_new * 3 * row_b
-            hk.copy_2d(kc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + row_b, 3 * row_b, row_b, S_new)
-            hk.copy_2d(vc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + 2 * row_b, 3 * row_b, row_b, S_new)
         o = torch.empty((M, d), device=self.device, dtype=torch.bfloat16)
-        hk.attn_fwd(qkv[:, :d], kc, vc, o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True, 1.0 / math.sqrt(hd), key_mask=kmask)
+        if len(cache) == 4:
+            # kv_cache="fp8", prefill only: attention reads the exact bf16 K / V of the prompt straight out of `qkv` (desc: kv_off = b * S_new),
+            # so the prompt's logits are those of the bf16-cache mode bit for bit; the rows enter the cache as codes + scale bytes
+            assert ctx == 0, "the kv8 cache has no multi-row step after the prefill (generate() rejects batch > 16)"
+            kc8, vc8, ks, vs = cache
+            hk.attn_fwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True,
+                        1.0 / math.sqrt(hd), key_mask=kmask)
+            for b in range(B):
+                rows = qkv[b * S_new:(b + 1) * S_new]
+                hk.kv8_quant_rows(rows[:, d:2 * d], kc8, ks, b * max_ctx, H)
+                hk.kv8_quant_rows(rows[:, 2 * d:], vc8, vs, b * max_ctx, H)
+        else:
+            kc, vc = cache
+            row_b = d * 2
+            for b in range(B):  # append the new K / V rows of sequence b at position ctx of its cache
+                src = qkv.data_ptr() + b * S_new * 3 * row_b
+                hk.copy_2d(kc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + row_b, 3 * row_b, row_b, S_new)
+                hk.copy_2d(vc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + 2 * row_b, 3 * row_b, row_b, S_new)
+            hk.attn_fwd(qkv[:, :d], kc, vc, o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True, 1.0 / math.sqrt(hd), key_mask=kmask)
         if li is not None:
             x = self._lin(li, "o", o, L["o_w"], residual=x)
             h = hk.rmsnorm_fwd(x, L["ln2_w"], self.eps, out=h)
@@ -863,7 +875,31 @@ class TextModal:
         self.base8, self.base_int8 = True, False
         return self
 
-    def _decode_session(self, B, max_ctx, caches, max_new, weights="bf16", kmask=None, lora=None):
+    def _check_kv_cache(self, kv_cache, rows, num_beams=1):
+        """generate(kv_cache=...): "bf16" or "fp8" (the kv8 format of csrc/decode_kv8.hip); what "fp8" cannot serve raises here, before anything is
+        allocated or enqueued.  rows = batch * num_beams."""
+        if kv_cache not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache={kv_cache!r}: expected 'bf16' or 'fp8'")
+        if kv_cache == "bf16":
+            return
+        if self.hd != 128:
+            raise ValueError(f'kv_cache="fp8" needs head_dim 128 (one scale byte per 128-value head row), this model has head_dim {self.hd}')
+        if rows > 16:
+            raise ValueError(f'kv_cache="fp8" with batch (x num_beams) {rows} > 16: beyond 16 rows the single-token step attends through attn_fwd '
+                             'over bf16 caches, which the fp8 cache does not have')
+        if num_beams > 1 and self.heads % 16:
+            raise ValueError(f'kv_cache="fp8" with num_beams > 1 needs a head count that is a multiple of 16 (kv_beam_reorder moves the scale '
+                             f'bytes of a position in 16-byte chunks), this model has {self.heads} heads')
+
+    def _alloc_kv(self, rows, kv_cache):
+        """per layer: (K, V) bf16 [rows, d], or for kv_cache="fp8" (K codes, V codes uint8 [rows, d], K scales, V scales uint8 [rows, H])"""
+        dev, d, H, n = self.device, self.d, self.heads, len(self.p["layers"])
+        if kv_cache == "fp8":
+            return [(torch.empty((rows, d), device=dev, dtype=torch.uint8), torch.empty((rows, d), device=dev, dtype=torch.uint8),
+                     torch.empty((rows, H), device=dev, dtype=torch.uint8), torch.empty((rows, H), device=dev, dtype=torch.uint8)) for _ in range(n)]
+        return [(torch.empty((rows, d), device=dev, dtype=torch.bfloat16), torch.empty((rows, d), device=dev, dtype=torch.bfloat16)) for _ in range(n)]
+
+    def _decode_session(self, B, max_ctx, caches, max_new, weights="bf16", kmask=None, lora=None, kv_cache="bf16"):
         """Static buffers + one captured hipGraph for the single-token step (batch <= 16): embedding gather, 32 x [RMSNorm,
         QKV GEMV, RoPE, KV append, attention over the cache, O GEMV + residual, RMSNorm, gate|up GEMV, SwiGLU, down GEMV +
         residual], final norm, lm_head GEMV -> fp32 logits.  Context length / positions live on the device
@@ -873,8 +909,13 @@ class TextModal:
         `hk.lora_down` on the activation the base product sees, the GEMV of whatever weight format into the fp32 `s.acc` without its residual,
         `hk.lora_up` into the linear's output with the residual: y = bf16(x W^T + (s x A^T) B^T + residual) on one fp32 value, what training's
         `_lin` computes.  The session reads the store's bf16 shadow and `Bfull` in place (`LoraStore.refresh` rewrites their storage), so it
-        holds no copy of an adapter; un-adapted groups and lm_head launch exactly what they launch without a store."""
+        holds no copy of an adapter; un-adapted groups and lm_head launch exactly what they launch without a store.
+
+        kv_cache="fp8": `caches` holds (K codes, V codes, K scale bytes, V scale bytes) per layer (`_alloc_kv`), and the attention of the step is
+        `hk.decode_attn_kv8` - one launch, like the bf16 kernels, with the same `nsplit`."""
         dev, d, ff, H, hd, V = self.device, self.d, self.ff, self.heads, self.hd, self.vocab
+        self._check_kv_cache(kv_cache, B)
+        kv8 = kv_cache == "fp8"
         bf = torch.bfloat16
         s = types.SimpleNamespace()
         s.B, s.max_ctx, s.max_new, s.caches = B, max_ctx, max_new, caches
@@ -1012,9 +1053,13 @@ class TextModal:
             hk.decode_advance(s.state, s.desc, s.pos, B, max_ctx, 1, self.cos, self.sin, cs)
             hk.gather_rows(self.p["embed"], s.tok32, out=s.x)
             x, x2 = s.x, s.x2
-            for li, (L, (kc, vc)) in enumerate(zip(self.p["layers"], caches)):
+            for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
                 lin(*W(L, "qkv_w"), x, s.qkv, d, hk.PRO_RMSNORM, L["ln1_w"], adapter=ad.get((li, "qkv")))
-                if hd == 128 and nsplit > 1:  # RoPE + KV append + attention over the cache in one launch, context split over workgroups
+                kc, vc = cache[:2]
+                if kv8:  # kv_cache="fp8": the same launch on e4m3 codes + scale bytes, the new rows quantised as they are appended
+                    hk.decode_attn_kv8(s.qkv, kc, vc, cache[2], cache[3], self.cos, self.sin, s.pos, s.o, B, H, hd, max_ctx, scale, nsplit,
+                                       getattr(s, "attn_part", None), getattr(s, "attn_tickets", None), key_mask=kmask, cs=cs)
+                elif hd == 128 and nsplit > 1:  # RoPE + KV append + attention over the cache in one launch, context split over workgroups
                     hk.decode_attn_split(s.qkv, kc, vc, self.cos, self.sin, s.pos, s.o, B, H, hd, max_ctx, scale, nsplit, s.attn_part,
                                          s.attn_tickets, key_mask=kmask, cs=cs)
                 elif hd == 128:
@@ -1055,7 +1100,7 @@ class TextModal:
     def generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p="default",
                  top_k="default", max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id="default",
                  return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1,
-                 length_penalty=1.0, early_stopping=False, return_beam_scores=False, adapters="merged", **_kw):
+                 length_penalty=1.0, early_stopping=False, return_beam_scores=False, adapters="merged", kv_cache="bf16", **_kw):
         """See `_generate`.  Two things happen here first: (1) `eos_token_id` defaults to the tokenizer's EOS, as HF `generate` stops on
         the generation config's EOS (pass None to disable); (2) if LoRA adapters are attached and not merged, `adapters` says how they run:
         "merged" (default) - on merged COPIES of the affected weights (`_lora_merged_layers`), the base weights come back untouched;
@@ -1071,9 +1116,17 @@ class TextModal:
         "mxfp4" - on any base: the decoder linears stream OCP MXFP4 copies (e2m1 codes + one e8m0 scale per 32 k, 0.53 B per weight, made by
         `pack_mx4_decode` from whatever bf16 weights the decoder holds at the first call - merged copies included) against per-row e4m3
         activations, dequantised and multiplied by the block-scaled MFMA itself (`hk.gemv_mx4`).  Lossy like "fp8" (the weights are rounded to
-        4 bits); lm_head stays bf16, and the prefill stays on the bf16 GEMMs in every mode."""
+        4 bits); lm_head stays bf16, and the prefill stays on the bf16 GEMMs in every mode.
+
+        `kv_cache`: "bf16" (default) or "fp8" - the K / V caches hold e4m3 codes and one e8m0 scale byte per head row (the kv8 format of
+        csrc/decode_kv8.hip: half the cache memory, half the cache stream of a step and of a beam reorder).  The prefill attends over the exact
+        bf16 K / V of the prompt, so its logits and the first token are those of "bf16"; from the second token on the step reads the rounded
+        cache (`hk.decode_attn_kv8`).  Works with every `weights` / `adapters` / sampler mode, left padding and beams; needs head_dim 128 and
+        batch x num_beams <= 16, else ValueError."""
         if adapters not in ("merged", "live"):
             raise ValueError(f"adapters={adapters!r}: expected 'merged' or 'live'")
+        nb_ = int(num_beams) if int(num_beams) >= 1 else 1
+        self._check_kv_cache(kv_cache, int(input_ids.shape[0]) * nb_, nb_)
         if eos_token_id == "default":
             eos_token_id = getattr(self.tokenizer, "eos_token_id", None)
         # sampling defaults of the reference's callers: HF GenerationConfig top_k = 50 and the Llama-2 generation_config.json top_p = 0.9
@@ -1086,7 +1139,7 @@ class TextModal:
                   top_k=top_k, max_new_tokens=max_new_tokens, use_cache=use_cache, stopping_criteria=stopping_criteria, streamer=streamer,
                   eos_token_id=eos_token_id, return_logits=return_logits, use_graph=use_graph, weights=weights, sampler=sampler, seed=seed,
                   repetition_penalty=repetition_penalty, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
-                  return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1))
+                  return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1), kv_cache=kv_cache)
         if self.lora is None:
             return self._generate(input_ids, **kw)
         if adapters == "live":   # nothing is merged or swapped: the bf16 base weights serve prefill, `weights` picks the decode stream, dropout is off
@@ -1111,7 +1164,8 @@ class TextModal:
     def _generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p=None,
                   top_k=None, max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id=None,
                   return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1,
-                  length_penalty=1.0, early_stopping=False, return_beam_scores=False, num_return_sequences=1, live_lora=False, **_kw):
+                  length_penalty=1.0, early_stopping=False, return_beam_scores=False, num_return_sequences=1, live_lora=False, kv_cache="bf16",
+                  **_kw):
         """TextModal.generate (text_modal.py:528-627): prefill over the spliced embeddings, then one token at a time with
         a KV cache; returns only the NEW token ids [B, n_new] (HF generate started from inputs_embeds).  Greedy
         (do_sample=False, the evaluation scripts' mode) runs entirely in HIP kernels; with do_sample=True the HIP-computed
@@ -1132,7 +1186,8 @@ class TextModal:
         if int(num_beams) != 1:
             return self._generate_beam(input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer,
                                        eos_token_id, return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty,
-                                       early_stopping, return_beam_scores, num_return_sequences, live_lora)
+                                       early_stopping, return_beam_scores, num_return_sequences, live_lora, kv_cache)
+        self._check_kv_cache(kv_cache, int(input_ids.shape[0]))
         pen = float(repetition_penalty)
         device_pick = (sampler == "device" and do_sample) or pen != 1.0
         if streamer is not None and getattr(streamer, "skip_prompt", False):
@@ -1150,8 +1205,7 @@ class TextModal:
             # (spliced) attention_mask is 0; every generated position is visible.
             kmask = torch.ones((B, max_ctx), device=dev, dtype=torch.uint8)
             kmask[:, :S0] = mask.to(device=dev, dtype=torch.uint8)
-        caches = [(torch.empty((B * max_ctx, d), device=dev, dtype=torch.bfloat16), torch.empty((B * max_ctx, d), device=dev, dtype=torch.bfloat16))
-                  for _ in range(len(self.p["layers"]))]
+        caches = self._alloc_kv(B * max_ctx, kv_cache)
 
         lora = self.lora if live_lora else None   # adapters="live": the store the session and the GEMM steps read
         s, seen, step_dev = None, None, None
@@ -1160,7 +1214,7 @@ class TextModal:
             if pen != 1.0:  # bitmap of the tokens generated so far in this call (HF started from inputs_embeds: the prompt is not in it)
                 seen = torch.zeros((B, (self.vocab + 31) // 32), device=dev, dtype=torch.int32)
             if B <= 16:  # the draw's step counter is the session's count of emitted tokens, on the device
-                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora)
+                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora, kv_cache)
                 s.state[0], s.state[1] = S0, 0
                 step_dev = s.state[1:2]
 
@@ -1176,7 +1230,8 @@ class TextModal:
             return torch.multinomial(torch.softmax(warp_logits(logits, temperature, top_k, top_p), -1), 1).squeeze(1)
 
         # ---- prefill (GEMM path) -> logits of the last prompt position -> first new token
-        desc = hk.make_desc([(b * S0, S0, b * max_ctx, S0, S0, 0) for b in range(B)], dev)
+        # kv_cache="fp8": the prompt's attention reads K / V out of the qkv buffer itself, where sequence b starts at row b * S0
+        desc = hk.make_desc([(b * S0, S0, b * (S0 if kv_cache == "fp8" else max_ctx), S0, S0, 0) for b in range(B)], dev)
         x = embeds.reshape(B * S0, d)
         for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
             x = self._layer_step(L, x, B, S0, 0, cache, desc, max_ctx, kmask, li=li if lora is not None else None)
@@ -1202,7 +1257,7 @@ class TextModal:
         n_done = 1
         if B <= 16:
             if s is None:
-                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora)
+                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora, kv_cache)
                 s.state[0], s.state[1] = S0, 0
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream())
@@ -1266,7 +1321,7 @@ class TextModal:
 
     def _generate_beam(self, input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer, eos_token_id,
                        return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty, early_stopping, return_beam_scores,
-                       num_return_sequences, live_lora=False):
+                       num_return_sequences, live_lora=False, kv_cache="bf16"):
         """Deterministic beam search, HF `generate(num_beams=nb, do_sample=False)` (generation/utils.py _beam_search; the web UI's
         answer_prepare kwargs): the prompt is prefilled ONCE per batch row into cache row b * nb and replicated to the row's other beams by
         `hk.kv_beam_reorder`; every further token is one linear single-stream graph of [model step over B * nb rows, beam_topk_rows, beam_step,
@@ -1287,6 +1342,7 @@ class TextModal:
             raise ValueError(f"num_return_sequences={num_return_sequences!r}: only the best hypothesis of each row is returned")
         if early_stopping not in (False, True):
             raise ValueError(f"early_stopping={early_stopping!r}: False or True ('never' is not implemented)")
+        self._check_kv_cache(kv_cache, int(input_ids.shape[0]) * nb, nb)
         embeds, _, mask, _ = self.prepare_inputs_for_multimodal(input_ids, attention_mask, None, image_embedding)
         B, S0, d = embeds.shape
         R = B * nb
@@ -1301,16 +1357,21 @@ class TextModal:
             kmask = torch.ones((B, max_ctx), device=dev, dtype=torch.uint8)
             kmask[:, :S0] = mask.to(device=dev, dtype=torch.uint8)
             kmask_r = kmask.repeat_interleave(nb, 0).contiguous()
-        caches = [(torch.empty((R * max_ctx, d), device=dev, dtype=torch.bfloat16), torch.empty((R * max_ctx, d), device=dev, dtype=torch.bfloat16))
-                  for _ in range(len(self.p["layers"]))]
+        kv8 = kv_cache == "fp8"
+        caches = self._alloc_kv(R * max_ctx, kv_cache)
         lora = self.lora if live_lora else None
-        s = self._decode_session(R, max_ctx, caches, max_new_tokens, weights, kmask_r, lora)
+        s = self._decode_session(R, max_ctx, caches, max_new_tokens, weights, kmask_r, lora, kv_cache)
         s.state[0], s.state[1] = S0, 0
         st = hk.BeamState(B, nb, V, max_new_tokens, length_penalty, dev)
-        table = hk.kv_cache_table(caches, dev)
+        # kv_beam_reorder is a byte copy in 16-byte chunks whose `d` counts 2-byte units: the bf16 caches with d, the kv8 code caches with d / 2
+        # and the scale arrays with H / 2 - codes and scales move together, in two launches
+        if kv8:
+            tables = [(hk.kv_cache_table([c[:2] for c in caches], dev), d // 2), (hk.kv_cache_table([c[2:] for c in caches], dev), self.heads // 2)]
+        else:
+            tables = [(hk.kv_cache_table(caches, dev), d)]
 
         # ---- prefill: sequence b into cache row b * nb (a cache "row" of nb * max_ctx positions), logits of the last prompt position
-        desc = hk.make_desc([(b * S0, S0, b * nb * max_ctx, S0, S0, 0) for b in range(B)], dev)
+        desc = hk.make_desc([(b * S0, S0, b * (S0 if kv8 else nb * max_ctx), S0, S0, 0) for b in range(B)], dev)
         x = embeds.reshape(B * S0, d)
         for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
             x = self._layer_step(L, x, B, S0, 0, cache, desc, nb * max_ctx, kmask, li=li if lora is not None else None)
@@ -1321,7 +1382,8 @@ class TextModal:
         def beam_tail(lg, t0, t1):
             hk.beam_topk_rows(lg, st, pen)
             hk.beam_step(st, s.next_ids, eos_token_id, early_stopping)
-            hk.kv_beam_reorder(table, B, nb, max_ctx, d, st.parent, t0, t1, S0 if t0 == 0 else max_new_tokens, done=st.bstate[1:2])
+            for table, units in tables:
+                hk.kv_beam_reorder(table, B, nb, max_ctx, units, st.parent, t0, t1, S0 if t0 == 0 else max_new_tokens, done=st.bstate[1:2])
             hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, R, max_new_tokens)
 
         def step():

@@ -252,6 +252,9 @@ class UniBind:
                  stopping_criteria=None, **kwargs):
         """UniBind.generate (lhrs/models/UniBind.py:214-242): encode the image once, then TextModal.generate."""
         assert hasattr(self, "text"), "text modal is not activate"
+        if "kv_cache" in kwargs:  # what the fp8 cache cannot serve raises before the image is encoded
+            nb = max(int(kwargs.get("num_beams", 1)), 1)
+            self.text._check_kv_cache(kwargs["kv_cache"], int(input_ids.shape[0]) * nb, nb)
         image_embedding = self.encode_image(images, pool=False) if images is not None else None  # None: text-only turn
         return self.text.generate(input_ids=input_ids, image_embedding=image_embedding, do_sample=do_sample, temperature=temperature,
                                   max_new_tokens=max_new_tokens, streamer=streamer, use_cache=use_cache,

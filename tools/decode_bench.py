@@ -18,6 +18,9 @@
                                                                                  from a model without derived copies and is timed on its own (merged
                                                                                  pays its merge and re-tiling there), with its peak allocated bytes;
                                                                                  merged + 4bit does not exist and prints "n/a: raises"
+    python tools/decode_bench.py 256 bf16,4bit 8 --kv-cache bf16,fp8 --repeats 3   A/B of the KV cache formats (generate(kv_cache=...)): the entries
+                                                                                 alternate inside every repeat; each mode's warm-up call is followed
+                                                                                 by its peak allocated bytes over one more 4-token call
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,6 +40,7 @@ ap.add_argument("--beam-only", action="store_true", help="with --num-beams: mode
 ap.add_argument("--lora-r", type=int, default=0, help="> 0: attach un-merged LoRA adapters of this rank (alpha = 2 r, random A and B)")
 ap.add_argument("--lora-targets", default="all", help="q,k,v,o | all (every decoder linear)")
 ap.add_argument("--adapters", default="merged", help="merged | live | a comma list that alternates (generate(adapters=...); needs --lora-r)")
+ap.add_argument("--kv-cache", default="bf16", help="bf16 | fp8 | a comma list that alternates (generate(kv_cache=...))")
 a = ap.parse_args()
 new, B = a.new, a.batch
 weight_modes = a.weights.split(",")
@@ -51,6 +55,8 @@ if "4bit" in weight_modes:
     model.text.quantize_base(4, quant_type="nf4", double_quant=True)
 adapter_modes = a.adapters.split(",") if a.lora_r > 0 else [None]
 assert all(m in ("merged", "live", None) for m in adapter_modes), a.adapters
+kv_modes = a.kv_cache.split(",")
+assert all(m in ("bf16", "fp8") for m in kv_modes), a.kv_cache
 if a.lora_r > 0:
     targets = ("q", "k", "v", "o", "gate", "up", "down") if a.lora_targets == "all" else tuple(a.lora_targets.split(","))
     lora = model.enable_lora(r=a.lora_r, alpha=2 * a.lora_r, targets=targets, seed=0)
@@ -84,12 +90,14 @@ def token_bytes_mxfp4():
     return total
 
 
-def kwargs(mode, weights, adapters=None):
+def kwargs(mode, weights, adapters=None, kv_cache="bf16"):
     # eos_token_id=None in EVERY mode (as bench.py --decode and cli_qa.py --synthetic-prompt time it): with an EOS the host synchronises on every
     # token and torch operators run between the graph replay and decode_emit, whoever picks the token
     kw = dict(do_sample=False, weights=weights, eos_token_id=None)
     if adapters is not None:
         kw.update(adapters=adapters)
+    if kv_cache != "bf16":
+        kw.update(kv_cache=kv_cache)
     if mode == "beam":
         kw.update(num_beams=a.num_beams)
     elif mode not in ("off", "rows"):
@@ -125,21 +133,30 @@ for mode in modes:
             if ad == "merged" and weights == "4bit":
                 print(f"[{weights}, batch {B}, adapters merged] n/a: raises (merged 16-bit copies have no 4-bit form)", flush=True)
                 continue
-            runs.append((mode, weights, ad))
-for mode, weights, ad in runs:
+            for kvc in kv_modes:
+                runs.append((mode, weights, ad, kvc))
+for mode, weights, ad, kvc in runs:
     if ad is not None:               # first call of an adapter mode, from a clean model: merge / re-tiling / capture cost and the peak footprint
         drop_derived_copies()
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
-    model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=4, **kwargs(mode, weights, ad))
+    model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=4, **kwargs(mode, weights, ad, kvc))
     if ad is not None:
         torch.cuda.synchronize()
         print(f"[{weights}, batch {B}, adapters {ad}] first call (4 new tokens) {time.perf_counter() - t0:.3f}s, peak allocated "
               f"{torch.cuda.max_memory_allocated() / 1e9:.2f} GB", flush=True)
+    if len(kv_modes) > 1 and mode != "beam":   # (beam search takes no stopping criteria) the caches of a NEW-token call, on top of what is resident after the warm-up: one more short call with the full context
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=new, **kwargs(mode, weights, ad, kvc), stopping_criteria=[lambda *_: True])
+        torch.cuda.synchronize()
+        print(f"[{weights}, batch {B}, kv_cache {kvc}] a call with room for {new} new tokens: peak allocated {torch.cuda.max_memory_allocated() / 1e9:.3f} GB, "
+              f"{(torch.cuda.max_memory_allocated() - base) / 1e9:.3f} GB above the resident {base / 1e9:.3f} GB", flush=True)
 if len(adapter_modes) > 1:           # the alternating timed runs keep every mode's copies resident: rebuild them all once, untimed
-    for mode, weights, ad in runs:
-        model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=4, **kwargs(mode, weights, ad))
+    for mode, weights, ad, kvc in runs:
+        model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=4, **kwargs(mode, weights, ad, kvc))
 roofline = {"fp8": "6.74 GB/token @ 8 TB/s = 1190 tok/s", "bf16": "13.5 GB/token @ 8 TB/s = 590 tok/s"}
 if "4bit" in weight_modes:
     gb = token_bytes_4bit() / 1e9
@@ -149,14 +166,16 @@ if "mxfp4" in weight_modes and "qkv_wmx4" in model.text.p["layers"][0]:   # with
     roofline["mxfp4"] = f"{gb:.3g} GB/token @ 8 TB/s = {8000 / gb:.0f} tok/s"
 roofline.setdefault("mxfp4", "n/a (the MXFP4 copies belong to the merged layers)")
 for _ in range(a.repeats):
-    for mode, weights, ad in runs:
+    for mode, weights, ad, kvc in runs:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=new, **kwargs(mode, weights, ad))
+        out = model.generate(inputs(mode)[0], images=inputs(mode)[1], max_new_tokens=new, **kwargs(mode, weights, ad, kvc))
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         n_new = out.shape[1]
         name = {"off": "greedy", "beam": f"beam search x{a.num_beams}", "rows": f"greedy, {out.shape[0]} rows"}.get(mode, f"sampled/{mode}")
         if ad is not None:
             name += f", adapters {ad}"
+        if len(kv_modes) > 1 or kvc != "bf16":
+            name += f", kv_cache {kvc}"
         print(f"[{weights}, batch {B}, {name}] {B}x{n_new} new tokens in {dt:.3f}s = {B*n_new/dt:.1f} tok/s (incl. ViT+pooler+prefill of {60-1+144} positions); HBM roofline " + roofline[weights] + " per sequence", flush=True)
