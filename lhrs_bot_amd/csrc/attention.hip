@@ -1091,6 +1091,8 @@ extern "C" int lhrs_attn_fwd(const void* q, long ldq, const void* k, long ldk, c
 
 // forward with an HF-style attention_mask: key j of sequence s is visible iff key_mask[s * ld_mask + j] != 0 (AND causal, AND
 // j < kv_len).  A query row with no visible key returns 0 (HF would return the mean of V: such rows are pad positions).
+// The K and V rows of a masked key j < kv_len ARE read: its score is replaced, but its V row goes through the P.V MFMA with a weight of
+// exactly 0, so it must hold finite values (a NaN or Inf there reaches the output).  Rows >= kv_len are never read.
 extern "C" int lhrs_attn_fwd_kmask(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo,
                                    float* lse, const int* desc, int nseq, int H, int D, int max_q, int max_kv, int LTq,
                                    int causal, float scale, const unsigned char* key_mask, long ld_mask, void* stream) {
