@@ -377,7 +377,7 @@ def path_of(entry, M, N, K, *, K2=0, bias=False, res=False, act=0, out_f32=False
             ldc=None, ldr=None, al16_ptrs=True, ff=None, ld_gu=None, ld_act=None, rope_cols=0, head_dim=128, cus=256, workspace=True):
     """The host dispatch of one call restated -> Plan.  entry: 'nt' (lhrs_gemm_bf16_nt), 'lora' (lhrs_gemm_bf16_nt_lora), 'mask'
     (lhrs_gemm_bf16_nt_dropmask), 'swiglu_fwd' / 'swiglu_bwd' (N ignored: ff), 'rope' (lhrs_gemm_rope_fwd), 'fp8' (lhrs_gemm_fp8_nt(_lora)),
-    'splitk_f32' (lhrs_gemm_bf16_nt_splitk_f32).  al16_ptrs: every operand / result pointer 16-byte aligned.  Kernels: 'u4', 'splitk_tail',
+    'splitk_f32' (lhrs_gemm_bf16_nt_splitk_f32), 'int8' (lhrs_gemm_int8_nt: always one 'i8_256' segment).  al16_ptrs: every operand / result pointer 16-byte aligned.  Kernels: 'u4', 'splitk_tail',
     '256', '144', 't128', 't64x128', 't64x64' (the small tiles), 'u4_swiglu_fwd' ..., 'swiglu_fwd_256' ..., 'fp8_256', 'fp8_small',
     'splitk_f32'; the SwiGLU and RoPE elementwise passes of the unfused fallbacks are no GEMM launches and are not listed."""
     P = Plan()
@@ -424,6 +424,8 @@ def path_of(entry, M, N, K, *, K2=0, bias=False, res=False, act=0, out_f32=False
             P.add(Mm, M, "fp8_small")
         else:
             P.add(0, M, "fp8_256")
+    elif entry == "int8":
+        P.add(0, M, "i8_256")      # gemm_fp8_launch takes no tail split when i8: the small-tile sibling exists for e4m3 only
     elif entry == "splitk_f32":
         if splitk_splits(M, N, K) == 1:
             _gemm_launch(P, 0, M, N, K, out_f32=True, ldc=ldc, **kw)
@@ -508,6 +510,7 @@ def reachable_paths(cus=256):
                     cells.add((entry, path_of(entry, M, N, K, cus=cus, **kw).kernels()))
                 if N % 8 == 0 and K % 128 == 0 and K >= 256:
                     cells.add(("fp8", path_of("fp8", M, N, K, cus=cus).kernels()))
+                    cells.add(("int8", path_of("int8", M, N, K, cus=cus).kernels()))
                 if N % 256 == 0:
                     cells.add(("rope", path_of("rope", M, N, K, rope_cols=N // 2, cus=cus).kernels()))
                     cells.add(("rope", path_of("rope", M, N, K, K2=64, rope_cols=N // 2, cus=cus).kernels()))

@@ -265,6 +265,7 @@ def test_path_of_hand_worked_shapes():
     assert P("rope", 4000, 4096, 4096, rope_cols=2048).kernels() == ("u4_rope",)
     assert P("rope", 2184, 4096, 4096, rope_cols=2048).kernels() == ("rope_144",)
     assert P("fp8", 8736, 4096, 4096).segments == [(0, 8192, "fp8_256"), (8192, 8736, "fp8_small")]
+    assert P("int8", 8736, 4096, 4096).segments == [(0, 8736, "i8_256")] and P("int8", 1, 8, 256).launches == 1   # no tail split for int8
     assert P("splitk_f32", 2048, 1024, 27392).kernels() == ("splitk_f32",) and P("splitk_f32", 256, 128, 640).kernels() == ("t64x64",)
 
 
@@ -272,5 +273,6 @@ def test_reachable_cells():
     cells = gc.reachable_cells()
     kernels = {k for _, ks in gc.reachable_paths() for k in ks}
     assert {k for _, k in cells} <= kernels | {"unfused"} and ("rope", "unfused") in cells and ("lora", "144") in cells
+    assert ("int8", "i8_256") in cells and {k for e, k in cells if e == "int8"} == {"i8_256"}
     assert kernels >= {"u4", "splitk_tail", "256", "144", "t128", "t64x128", "t64x64", "u4_swiglu_fwd", "swiglu_fwd_256", "swiglu_fwd_144",
-                       "u4_swiglu_bwd", "swiglu_bwd_256", "swiglu_bwd_144", "u4_rope", "rope_256", "rope_144", "fp8_256", "fp8_small"}, kernels
+                       "u4_swiglu_bwd", "swiglu_bwd_256", "swiglu_bwd_144", "u4_rope", "rope_256", "rope_144", "fp8_256", "fp8_small", "i8_256"}, kernels

@@ -18,6 +18,7 @@ from lhrs_bot_amd import _lib
 from lhrs_bot_amd import kernels as hk
 
 import gemm_cases as gc
+import int8_cases as ic
 
 pytestmark = pytest.mark.gpu
 
@@ -301,6 +302,133 @@ def test_gemm_fp8_path(case):
     untouched(buf, M, N, 0, name)
 
 
+# the kernel body at its small edges: K = 256 (two stages, the minimum), K = 384 (an odd stage count), one and three bf16 stages behind them
+FP8_EDGES = [("k256_ragged_no_pair", 257, 264, 256, 0), ("k384_pair64_res_alpha", 300, 520, 384, 64), ("k384_pair192_res_alpha", 70, 264, 384, 192)]
+
+
+@pytest.mark.parametrize("case", FP8_EDGES, ids=[c[0] for c in FP8_EDGES])
+def test_gemm_fp8_edge_shapes(case):
+    name, M, N, K, K2 = case
+    g = Gen(M + N + K + K2 + 6)
+    A8, sa = e4m3_rows(g, M, K, 1.0)
+    B8, sb = e4m3_rows(g, N, K, K ** -0.5)
+    A2 = g.mat(M, K2, pad=72) if K2 else None                 # NaN in a whole stage past K2
+    B2 = g.mat(N, K2, 0.5 * K2 ** -0.5, pad=72) if K2 else None
+    res = g.mat(M, N, 0.5) if K2 else None
+    alpha = 0.5 if K2 else 1.0
+    buf, C = out_buf(M, N)
+    plan = gc.path_of("fp8", M, N, K, K2=K2)
+    assert plan.kernels() == ("fp8_256",)
+    L = _lib.load()
+    s = hk._stream()
+    if K2:
+        fn = lambda: _lib.check(L.lhrs_gemm_fp8_nt_lora(A8.data_ptr(), A8.stride(0), sa.data_ptr(), B8.data_ptr(), B8.stride(0), sb.data_ptr(),
+                                                        A2.data_ptr(), A2.stride(0), B2.data_ptr(), B2.stride(0), K2, C.data_ptr(), C.stride(0),
+                                                        M, N, K, res.data_ptr(), res.stride(0), float(alpha), s), "fp8_lora")
+    else:
+        fn = lambda: _lib.check(L.lhrs_gemm_fp8_nt(A8.data_ptr(), A8.stride(0), sa.data_ptr(), B8.data_ptr(), B8.stride(0), sb.data_ptr(),
+                                                   C.data_ptr(), C.stride(0), M, N, K, None, 0, float(alpha), s), "fp8")
+    run_checked(plan, name, fn)
+    gc.check("bf16", C, gc.ref_fp8(A8, sa, B8, sb, alpha=alpha, residual=res, A2=A2, B2=B2), plan.segments, what=name)
+    untouched(buf, M, N, 0, name)
+
+
+# ------------------------------------------------------------------------------------------------------------- LLM.int8
+
+INT8 = [
+    # name, M, N, K, host K2, device k2 (None: no k2_dev pointer), flags
+    ("min_shape_no_pair", 1, 8, 256, 0, None, dict()),
+    ("ragged_device_stage", 257, 264, 256, 0, 64, dict()),
+    ("odd_stages_host_pair_device_zero_res_alpha", 300, 520, 384, 64, 0, dict(res=True, alpha=0.5)),
+    ("odd_plus_odd_stages_res", 70, 264, 384, 192, 128, dict(res=True)),
+    ("long_k_device_stage", 40, 64, 24832, 0, 64, dict()),
+    ("device_count_equals_k", 256, 256, 512, 0, 512, dict()),
+]
+
+
+def int8_rows(g, rows, K, scale):
+    """int8 codes uniform in +-127 in a [rows, K + 16] buffer (127 in the padding bytes) and positive per-row factors around scale / 127"""
+    buf = torch.full((rows, K + 16), 127, dtype=torch.int8)
+    buf[:, :K] = torch.randint(-127, 128, (rows, K), generator=g.g).to(torch.int8)
+    s = (0.5 + torch.rand(rows, generator=g.g)) * (scale / 127.0)
+    return buf.to(DEV)[:, :K], s.to(DEV)
+
+
+@pytest.mark.parametrize("case", INT8, ids=[c[0] for c in INT8])
+def test_gemm_int8_path(case):
+    name, M, N, K, K2, k2, f = case
+    g = Gen(M + N + K + K2 + 7)
+    A8, sa = int8_rows(g, M, K, 1.0)
+    B8, sb = int8_rows(g, N, K, 0.02)
+    rms = (73.0 / 127.0) ** 2 * 0.02 * K ** 0.5                 # of the 8-bit term: codes uniform in +-127 have RMS ~73
+    K2t = K2 + (k2 or 0)
+    pair = K2 > 0 or k2 is not None
+    A2 = g.mat(M, K2t, 1.0, pad=72) if pair else None          # NaN in a whole stage past K2 + k2
+    B2 = g.mat(N, K2t, 0.5 * rms * max(K2t, 1) ** -0.5, pad=72) if pair else None
+    k2_dev = torch.tensor([k2], dtype=torch.int32, device=DEV) if k2 is not None else None
+    res = g.mat(M, N, 0.5 * rms) if f.get("res") else None
+    alpha = f.get("alpha", 1.0)
+    buf, C = out_buf(M, N)
+    plan = gc.path_of("int8", M, N, K, K2=K2)
+    L = _lib.load()
+    p = hk._p
+    fn = lambda: _lib.check(L.lhrs_gemm_int8_nt(A8.data_ptr(), A8.stride(0), sa.data_ptr(), B8.data_ptr(), B8.stride(0), sb.data_ptr(), p(A2),
+                                                A2.stride(0) if pair else 0, p(B2), B2.stride(0) if pair else 0, K2, p(k2_dev), C.data_ptr(),
+                                                C.stride(0), M, N, K, p(res), res.stride(0) if res is not None else 0, float(alpha),
+                                                hk._stream()), "gemm_int8_nt")
+    run_checked(plan, name, fn)
+    assert res is None or res.stride(0) > N
+    ref = ic.ref_int8(A8, sa, B8, sb, alpha=alpha, residual=res, A2=A2, B2=B2)
+    assert bool(torch.isfinite(C).all()), f"{name}: a column of A2 / B2 past K2 + k2 was read"
+    rep = gc.check("bf16", C, ref, plan.segments, what=name)
+    print(f"\nint8 GEMM {name}: element ratio at c = 1 {rep.elem:.4f}, cell rel-L2 {rep.cell:.3g}")
+    if K2t == 0 and res is None:
+        ok, ratio = ic.tight_bound_ok(C, ref.want)
+        print(f"int8 GEMM {name}: worst |err| / ((2^-8 + 2^-21) |want|) {ratio:.4f}")
+        assert ok, f"{name}: {ratio:.4f}x the derived bound"
+    if K2t == 0:        # exact integer sums, no bf16 stage: one correctly rounded value per element
+        emu = ic.emu_product(A8.cpu(), sa.cpu(), B8.cpu(), sb.cpu(), None, None, 0, alpha=alpha, residual=None if res is None else res.cpu())
+        assert torch.equal(ic.bits16(C.cpu()), ic.bits16(emu)), name
+    untouched(buf, M, N, 0, name)
+
+
+def test_gemm_int8_no_pair_residual_is_bit_exact():
+    """Without bf16 stages the product has one value per element: int32 sum, f32, (sa * alpha), sb, bf16, and the residual added in bf16 AFTER the
+    store (as gemm_fp8 does).  The element bound cannot tell that order from a residual added before the store; bit equality can."""
+    M, N, K = 70, 264, 384
+    g = Gen(M + N + K + 8)
+    A8, sa = int8_rows(g, M, K, 1.0)
+    B8, sb = int8_rows(g, N, K, 0.02)
+    res = g.mat(M, N, 0.1)
+    buf, C = out_buf(M, N)
+    L = _lib.load()
+    _lib.check(L.lhrs_gemm_int8_nt(A8.data_ptr(), A8.stride(0), sa.data_ptr(), B8.data_ptr(), B8.stride(0), sb.data_ptr(), None, 0, None, 0, 0, None,
+                                   C.data_ptr(), C.stride(0), M, N, K, res.data_ptr(), res.stride(0), 0.5, hk._stream()), "gemm_int8_nt")
+    torch.cuda.synchronize()
+    gc.check("bf16", C, ic.ref_int8(A8, sa, B8, sb, alpha=0.5, residual=res), what="int8 no pair, residual")
+    emu = ic.emu_product(A8.cpu(), sa.cpu(), B8.cpu(), sb.cpu(), None, None, 0, alpha=0.5, residual=res.cpu())
+    assert torch.equal(ic.bits16(C.cpu()), ic.bits16(emu))
+    untouched(buf, M, N, 0, "int8 no pair, residual")
+
+
+@pytest.mark.parametrize("K", [256, 384])
+def test_gemm_int8_k_mapping_probe(K):
+    """A8 = I (code 1 on the diagonal), unit factors: the result is B8^T exactly (integers up to 127 are exact in bf16).  Any disagreement
+    between the k a byte slot of A holds and the k the same slot of B holds moves or drops an element."""
+    N = 264
+    g = Gen(K + 9)
+    A8 = torch.eye(K, dtype=torch.int8).to(DEV)
+    B8, _ = int8_rows(g, N, K, 1.0)
+    ones_m, ones_n = torch.ones(K, device=DEV), torch.ones(N, device=DEV)
+    buf, C = out_buf(K, N)
+    L = _lib.load()
+    _lib.check(L.lhrs_gemm_int8_nt(A8.data_ptr(), A8.stride(0), ones_m.data_ptr(), B8.data_ptr(), B8.stride(0), ones_n.data_ptr(), None, 0, None, 0,
+                                   0, None, C.data_ptr(), C.stride(0), K, N, K, None, 0, 1.0, hk._stream()), "gemm_int8_nt")
+    torch.cuda.synchronize()
+    assert torch.equal(C.float(), B8.t().float())
+    untouched(buf, K, N, 0, f"int8 k-mapping K={K}")
+
+
 # ------------------------------------------------------------------------------------------------------------- f32 weight gradients
 
 def test_gemm_f32_weight_gradient_family():
@@ -349,6 +477,7 @@ def test_gemm_table_reaches_every_cell():
     paths += [("swiglu_bwd", gc.path_of("swiglu_bwd", M, 0, K, ff=ff).kernels()) for _, M, ff, K, _ in SWIGLU_BWD]
     paths += [("rope", gc.path_of("rope", M, N, K, K2=K2, rope_cols=2048, head_dim=hd).kernels()) for _, M, N, K, K2, hd in ROPE]
     paths += [("fp8", gc.path_of("fp8", M, N, K, K2=64 if full else 0).kernels()) for _, M, N, K, full in FP8]
+    paths += [("int8", gc.path_of("int8", M, N, K, K2=K2).kernels()) for _, M, N, K, K2, _, _ in INT8]
     reached = set().union(*(gc.cells_of(e, ks) for e, ks in paths))
     missing = gc.reachable_cells() - reached
     assert not missing, sorted(missing)
