@@ -8,7 +8,7 @@ flag-compatible (`-c Config/multi_modal_eval.yaml --model-path <FINAL.pt dir> --
 The prefill runs on the GEMM path, the per-token step is one captured hipGraph (lhrs_bot_amd/text.py `_decode_session`);
 `bits: 8` in the YAML (or `--opts bits 8`) streams e4m3 weights through the MFMA GEMV; `--decode-weights 4bit` with `bits: 4` streams
 the NF4 / FP4 codes of the 4-bit base (lhrs_gemv4); `--decode-weights mxfp4` (any base) streams OCP MXFP4 copies on the FP4 MFMA
-(lhrs_gemv_mx4).
+(lhrs_gemv_mx4); `--decode-weights int8` with `bits: 8` streams the int8 rows of the LLM.int8 base (lhrs_gemv_int8).
 
 Imports and call order follow /root/reference cli_qa.py:10-22, 84-193 over the `lhrs.*` surface.  Weights / tokenizer come from the paths
 in the YAML (`text.path`, `rgb_vision.vit_name`); when they are not on disk the towers are random-initialised and the word-hash
@@ -54,13 +54,15 @@ def parse_option(args=None):
     p.add_argument("--repetition-penalty", type=float, default=1.0, help="HF repetition_penalty over the generated tokens (the web UI uses 1.05)")
     p.add_argument("--num-beams", type=int, default=1, help="HF num_beams: > 1 answers by deterministic beam search on the device (no sampling, no token "
                                                             "stream: the answer is printed when the search ends); batch * num_beams <= 16")
-    p.add_argument("--decode-weights", default=None, choices=["bf16", "fp8", "4bit", "mxfp4"],
+    p.add_argument("--decode-weights", default=None, choices=["bf16", "fp8", "4bit", "mxfp4", "int8"],
                    help="what the single-token step streams (default: fp8 iff `bits: 8`, else bf16); 4bit reads the NF4 / FP4 codes of the `bits: 4` "
                         "base directly and requires it; if the decoder is not on that base yet (an evaluation run has not been through "
                         "prepare_for_training) it is put there first with the YAML's quant_type / double_quant, so the prefill too reads "
                         "the dequantised weights, as every product of the reference's Linear4bit does; mxfp4 (any base, no YAML key) streams OCP MXFP4 "
                         "copies of the decoder linears - e2m1 codes with one e8m0 scale per 32 weights, multiplied by the FP4 MFMA against e4m3 "
-                        "activations: lossy like fp8, lm_head and prefill stay bf16")
+                        "activations: lossy like fp8, lm_head and prefill stay bf16; int8 requires `bits: 8` on the LLM.int8 scheme (the reference's "
+                        "load_in_8bit) and streams the base's own int8 rows in bitsandbytes' MatMul8bitLt arithmetic, prefill included - if the decoder "
+                        "is not on that base yet it is put there first; the default for `bits: 8` stays fp8")
     p.add_argument("--adapters", default="merged", choices=["merged", "live"],
                    help="un-merged LoRA adapters (stage >= 1 with a TextLoRA/ loaded): merged = decode on merged 16-bit copies of the adapted weights; "
                         "live = no copies, the adapters run next to the base weights of whatever --decode-weights streams (4bit included)")
@@ -130,6 +132,14 @@ def main(config):
             raise ValueError("--decode-weights 4bit requires `bits: 4` in the YAML (or --opts bits 4)")
         if not model.text.base4:   # bits: 4 selects the storage in prepare_for_training; an evaluation run has not been through it
             model.text.quantize_base(4, quant_type=str(config.get("quant_type", "nf4")), double_quant=bool(config.get("double_quant", True)))
+    if weights == "int8":
+        if bits != 8:
+            raise ValueError("--decode-weights int8 requires `bits: 8` in the YAML (or --opts bits 8)")
+        if model.text.base8:
+            raise ValueError("--decode-weights int8 requires the LLM.int8 scheme of `bits: 8`, this decoder is on the e4m3 scheme "
+                             "(quantize_base(8, 'e4m3') / LHRS_BASE8=e4m3): use --decode-weights fp8, or load the base with the int8 scheme")
+        if not model.text.base_int8:   # an evaluation run has not been through prepare_for_training
+            model.text.quantize_base(8, "int8")
 
     if config.get("image_file"):
         image = load_image(config.image_file)

@@ -440,6 +440,30 @@ int lhrs_gemv_mx4(const void* codes_t, const void* scales_t, const void* x8, lon
  * inside the kernel, as lhrs_gemv_fp8_mfma_fused does them */
 int lhrs_gemv_mx4_fused(const void* codes_t, const void* scales_t, const void* x, long ldx, int prologue, const void* norm_w, float eps,
                         const void* residual, long ldr, void* y, long ldy, int B, int N, int K, int out_f32, void* stream);
+/* ---- decode from the LLM.int8 base (generate(weights="int8")): the int8 rows and row factors of lhrs_quant_int8_rows are the weight stream ----
+ * lhrs_int8_decode_prepare: the activation side of one decode linear in ONE launch, 1 <= B <= 16 rows, no host round trip (graph-capturable),
+ * every output in caller-owned buffers.  h = pro(x) with prologue / norm_w / eps as for lhrs_gemv, rounded to bf16 where its staging rounds
+ * (x is [B, 2K] for prologue 2).  The outputs are those of lhrs_int8_prepare(h) with M = B, bit for bit: a column is an outlier when any row
+ * holds |h| >= thr; sx[b] = max{|h[b,k]| : |h[b,k]| < thr} / 127 (0 for a row without a counted non-zero entry); xq = clip(rint(h *
+ * fl(127 / absmax)), +-127) with ties to even and the outlier columns stored as 0; idx = the outlier columns, ascending; xo[b, j] = h[b, idx[j]];
+ * meta[0] = n, the column count - no cap: idx holds K entries and ldo >= K.  Padding convention: none.  idx[0 .. n) and xo[:, 0 .. n) are
+ * written; entries past n keep what they held and lhrs_gemv_int8 reads none of them.  h_out (bf16 [B, ldh]) may be NULL.
+ * K % 64 == 0, K <= 16384; x / xq / h_out / norm_w 16-byte aligned, ldx % 8 == 0, ldh % 8 == 0, ldq % 16 == 0 (ldx, ldh, ldo in bf16, ldq in bytes). */
+int lhrs_int8_decode_prepare(const void* x, long ldx, int prologue, const void* norm_w, float eps, float thr, void* h_out, long ldh,
+                             void* xq, long ldq, float* sx, int* idx, int* meta, void* xo, long ldo, int B, int K, void* stream);
+/* int8 [N, ldw] rows -> the operand order lhrs_gemv_int8 streams with w_packed = 1 (K % 64 == 0, ldw % 16 == 0): out holds ceil(N/16) * K
+ * bytes as [ceil(N/16)][K/64][64 lanes][16 B]; lane (r, g) of step s holds WQ[16 rg + r][64 s + 16 g .. +16]; rows past N are zero. */
+int lhrs_repack_int8_mfma(const void* WQ, long ldw, void* out, int N, int K, void* stream);
+/* The weight stream on v_mfma_i32_16x16x64_i8, 1 <= B <= 16, K % 64 == 0:
+ *   t  = f32(sum_k xq[b,k] * WQ[n,k])                         exact int32 sum
+ *   t  = t * fl(sx[b] * wscale[n])                            the factor product first, then one multiply
+ *   t += sum_{j < n} f32(xo[b,j]) * f32(bf16(f32(WQ[n, idx[j]]) * wscale[n]))      fp32, n = meta[0] read on the device
+ *   y  = t + residual[b,n]                                    residual optional; ONE rounding to bf16, or an fp32 store with out_f32
+ * WQ: int8 [N, ldw] rows (w_packed 0) or the copy of lhrs_repack_int8_mfma (w_packed 1, ldw ignored).  No atomics, stored once, two runs are
+ * bit-equal.  WQ / xq 16-byte aligned, ldw % 16 == 0, ldq % 16 == 0; n is clamped to min(K, ldo). */
+int lhrs_gemv_int8(const void* WQ, long ldw, int w_packed, const float* wscale, const void* xq, long ldq, const float* sx,
+                   const int* idx, const int* meta, const void* xo, long ldo, const void* residual, long ldr, void* y, long ldy, int B,
+                   int N, int K, int out_f32, void* stream);
 /* single-token attention for generate() (HF LlamaAttention with a KV cache at q_len = 1, reached from TextModal.generate,
  * lhrs/models/text_modal.py:586-627): RoPE of the new q / k row at device-resident position pos[b], append of (k, v) to the caches
  * [B * max_ctx, H*128] and attention over keys 0..pos[b] (optionally AND an HF attention_mask byte row), in ONE launch. */

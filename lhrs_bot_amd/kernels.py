@@ -1328,6 +1328,101 @@ def gemv_mx4_fused(W: PackedMX4, x, out, K, *, prologue=PRO_NONE, norm_w=None, e
     return out
 
 
+class PackedI8:
+    """int8 weight rows [N, K] of `quant_int8_rows` re-tiled by `repack_int8_mfma` into the operand order of `gemv_int8`: int8
+    [ceil(N/16), K/64, 64, 16] - lane (r, g) of a 64-k step holds WQ[16 rg + r][64 step + 16 g .. +16]; rows past N are zero."""
+
+    def __init__(self, data, N, K):
+        self.data, self.N, self.K = data, N, K
+        self.shape = (N, K)
+
+    def nbytes(self) -> int:
+        return self.data.numel()
+
+
+def repack_int8_mfma(WQ) -> PackedI8:
+    """int8 [N, K] rows -> PackedI8 (K % 64 == 0)."""
+    _req(WQ, torch.int8, "repack_int8_mfma WQ")
+    if WQ.dim() != 2 or WQ.stride(1) != 1:
+        raise ValueError(f"repack_int8_mfma: WQ {tuple(WQ.shape)}: expected [N, K] with dense rows")
+    N, K = WQ.shape
+    out = torch.empty(((N + 15) // 16, max(K // 64, 1), 64, 16), device=WQ.device, dtype=torch.int8)
+    _lib.check(_L().lhrs_repack_int8_mfma(WQ.data_ptr(), WQ.stride(0), out.data_ptr(), N, K, _stream()), "repack_int8_mfma")
+    return PackedI8(out, N, K)
+
+
+class Int8DecodeWorkspace:
+    """Static buffers of the activation side of the int8 decode linears (`int8_decode_prepare` writes them, `gemv_int8` reads them), for up to
+    `B` rows of up to `kmax` columns: codes, row factors, the outlier column list, the gathered 16-bit activations and meta = [n]."""
+
+    def __init__(self, device, B: int, kmax: int, threshold: float = 6.0):
+        self.threshold, self.B, self.kmax = float(threshold), B, (kmax + 63) // 64 * 64
+        self.xq = torch.zeros((B, self.kmax), device=device, dtype=torch.int8)
+        self.sx = torch.zeros(B, device=device, dtype=torch.float32)
+        self.idx = torch.zeros(self.kmax, device=device, dtype=torch.int32)
+        self.xo = torch.zeros((B, self.kmax), device=device, dtype=torch.bfloat16)
+        self.meta = torch.zeros(2, device=device, dtype=torch.int32)
+
+
+def int8_decode_prepare(x, K, ws: Int8DecodeWorkspace, *, prologue=PRO_NONE, norm_w=None, eps=1e-5, h_out=None):
+    """The activation side of one decode linear on the LLM.int8 base in one launch (1 <= B <= 16): h = pro(x) (x is [B, 2K] for the SwiGLU
+    prologue), then what `lhrs_int8_prepare` computes on h, into `ws`: ws.xq[:B, :K], ws.sx[:B], ws.idx[:n], ws.xo[:B, :n], ws.meta[0] = n.
+    h_out: optional bf16 [B, K] that receives h."""
+    _req(x, torch.bfloat16, "int8_decode_prepare x")
+    if x.dim() != 2:
+        raise ValueError(f"int8_decode_prepare: x {tuple(x.shape)}: expected [B, K] ([B, 2K] for the SwiGLU prologue)")
+    B = x.shape[0]
+    if x.shape[1] != (2 * K if prologue == PRO_SWIGLU else K) or x.stride(1) != 1:
+        raise ValueError(f"int8_decode_prepare: x {tuple(x.shape)} for K={K}, prologue {prologue} (SwiGLU reads [B, 2K]); rows must be dense")
+    if B > ws.B or K > ws.kmax:
+        raise ValueError(f"int8_decode_prepare: {B} rows x {K} columns, the workspace holds {ws.B} x {ws.kmax}")
+    if prologue == PRO_RMSNORM:
+        if norm_w is None or norm_w.numel() != K or not norm_w.is_contiguous():
+            raise ValueError(f"int8_decode_prepare: the RMSNorm prologue needs a contiguous norm_w of {K} elements")
+        _req(norm_w, torch.bfloat16, "int8_decode_prepare norm_w")
+    if h_out is not None:
+        _req(h_out, torch.bfloat16, "int8_decode_prepare h_out")
+        if tuple(h_out.shape) != (B, K) or h_out.stride(1) != 1:
+            raise ValueError(f"int8_decode_prepare: h_out {tuple(h_out.shape)}, expected ({B}, {K}) with dense rows")
+    st = _L().lhrs_int8_decode_prepare(x.data_ptr(), x.stride(0), int(prologue), _p(norm_w), float(eps), ws.threshold, _p(h_out),
+                                       h_out.stride(0) if h_out is not None else 0, ws.xq.data_ptr(), ws.xq.stride(0), ws.sx.data_ptr(),
+                                       ws.idx.data_ptr(), ws.meta.data_ptr(), ws.xo.data_ptr(), ws.xo.stride(0), B, K, _stream())
+    _lib.check(st, "int8_decode_prepare")
+    return ws
+
+
+def gemv_int8(WQ, wscale, ws: Int8DecodeWorkspace, out, K, *, residual=None, out_f32=False):
+    """out[B, N] = f32(ws.xq @ WQ^T) * fl(ws.sx[b] * wscale[n]) + ws.xo[:, :n] @ bf16(WQ[:, ws.idx[:n]] * wscale)^T (+ residual), n = ws.meta[0]
+    read on the device; the int8 sum is exact (v_mfma_i32_16x16x64_i8), the 16-bit outlier term accumulates in fp32, one rounding at the store.
+    WQ: int8 [N, K] rows or a PackedI8; wscale fp32 [N] (`quant_int8_rows`); ws as left by `int8_decode_prepare`.  1 <= B <= 16, K % 64 == 0."""
+    _req(wscale, torch.float32, "gemv_int8 wscale")
+    _req(out, torch.float32 if out_f32 else torch.bfloat16, "gemv_int8 out")
+    if isinstance(WQ, PackedI8):
+        wp, ldw, N, pk = WQ.data.data_ptr(), 0, WQ.N, 1
+        if WQ.K != K or WQ.data.numel() != (N + 15) // 16 * 16 * K:
+            raise ValueError(f"gemv_int8: the tiled buffer does not belong to a weight of shape ({N}, {K})")
+    else:
+        _req(WQ, torch.int8, "gemv_int8 WQ")
+        if WQ.dim() != 2 or WQ.shape[1] != K or WQ.stride(1) != 1:
+            raise ValueError(f"gemv_int8: WQ {tuple(WQ.shape)} for K={K}; rows must be dense")
+        wp, ldw, N, pk = WQ.data_ptr(), WQ.stride(0), WQ.shape[0], 0
+    if out.dim() != 2:
+        raise ValueError(f"gemv_int8: out {tuple(out.shape)}: expected [B, {N}]")
+    B = out.shape[0]
+    if out.shape[1] != N or out.stride(1) != 1 or B > ws.B or K > ws.kmax or wscale.numel() < N:
+        raise ValueError(f"gemv_int8: out {tuple(out.shape)} / wscale {tuple(wscale.shape)} for a weight of shape ({N}, {K}) and a workspace "
+                         f"of {ws.B} x {ws.kmax}; rows must be dense")
+    if residual is not None:
+        _req(residual, torch.bfloat16, "gemv_int8 residual")
+        if tuple(residual.shape) != (B, N) or residual.stride(1) != 1:
+            raise ValueError(f"gemv_int8: residual {tuple(residual.shape)}, expected ({B}, {N}) with dense rows")
+    st = _L().lhrs_gemv_int8(wp, ldw, pk, wscale.data_ptr(), ws.xq.data_ptr(), ws.xq.stride(0), ws.sx.data_ptr(), ws.idx.data_ptr(),
+                             ws.meta.data_ptr(), ws.xo.data_ptr(), ws.xo.stride(0), _p(residual), residual.stride(0) if residual is not None else 0,
+                             out.data_ptr(), out.stride(0), B, N, K, int(out_f32), _stream())
+    _lib.check(st, "gemv_int8")
+    return out
+
+
 # --------------------------------------------------------------------------------------------- decode with live adapters
 LORA_DOWN_MAX_SLICES = 16
 LORA_DOWN_MAX_LDS = 160 * 1024 - 16   # bytes of staged activations a lora_down workgroup can hold (the CU's LDS less the kernel's static words)

@@ -277,7 +277,7 @@ class TextModal:
             self.quantize_base(4, quant_type=base4[0], double_quant=base4[1])   # peft re-quantises a merged Linear4bit the same way
 
     _W4_PARTS = {"qkv_w": 3, "o_w": 1, "gu_w": 2, "down_w": 1}   # reference Linears per fused weight (row-concatenated): 4-bit statistics are per Linear
-    DERIVED_SUFFIXES = ("p", "8", "8s", "8p", "i8", "i8s", "q4", "4p", "mx4")   # decode re-tilings and e4m3 copies of a weight `<name>` / `<name>T`, rebuilt lazily from it
+    DERIVED_SUFFIXES = ("p", "8", "8s", "8p", "i8", "i8s", "i8p", "q4", "4p", "mx4")   # decode re-tilings and e4m3 copies of a weight `<name>` / `<name>T`, rebuilt lazily from it
 
     def _drop_derived(self, L) -> None:
         """Forget every tensor that was computed FROM a decoder weight of layer dict `L` (decode re-tilings, e4m3 copies): after the weight
@@ -727,17 +727,20 @@ class TextModal:
     __call__ = decode
 
     # ------------------------------------------------------------------ generate (KV cache)
-    def _layer_step(self, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None):
+    def _layer_step(self, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None, int8=False):
         """One decoder layer over S_new new positions per sequence with `ctx` cached positions (prefill: ctx = 0).  li = the layer's index:
         generate(adapters="live") - every adapted group runs its adapters through the training forward (`_lin` / `_gu_fwd`: gemm_nt_skinny, then
-        the base GEMM with the (T, Bfull) pair on its accumulators) on the bf16 base weights; the caller has switched dropout off."""
+        the base GEMM with the (T, Bfull) pair on its accumulators) on the bf16 base weights; the caller has switched dropout off.
+        int8 (generate(weights="int8") only, li given): the four linears are the LLM.int8 products of the training forward (`hk.int8_linear` on
+        the int8 rows), the adapters of a live store on top."""
         d, H, hd, ff = self.d, self.heads, self.hd, self.ff
         M = x.shape[0]
+        i8 = (lambda name: (L[name + "i8"], L[name + "i8s"])) if int8 else (lambda name: None)
         h = hk.rmsnorm_fwd(x, L["ln1_w"], self.eps)
         if li is None:
             qkv = hk.gemm_rope_fwd(h, L["qkv_w"], self.cos, self.sin, pos_mod=S_new, pos0=ctx, rope_cols=2 * d, head_dim=hd)
         else:
-            qkv = self._lin(li, "qkv", h, L["qkv_w"], rope=(S_new, ctx))
+            qkv = self._lin(li, "qkv", h, L["qkv_w"], rope=(S_new, ctx), i8=i8("qkv_w"))
         o = torch.empty((M, d), device=self.device, dtype=torch.bfloat16)
         if len(cache) == 4:
             # kv_cache="fp8", prefill only: attention reads the exact bf16 K / V of the prompt straight out of `qkv` (desc: kv_off = b * S_new),
@@ -759,10 +762,10 @@ class TextModal:
                 hk.copy_2d(vc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + 2 * row_b, 3 * row_b, row_b, S_new)
             hk.attn_fwd(qkv[:, :d], kc, vc, o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True, 1.0 / math.sqrt(hd), key_mask=kmask)
         if li is not None:
-            x = self._lin(li, "o", o, L["o_w"], residual=x)
+            x = self._lin(li, "o", o, L["o_w"], residual=x, i8=i8("o_w"))
             h = hk.rmsnorm_fwd(x, L["ln2_w"], self.eps, out=h)
-            _, act, _ = self._gu_fwd(li, h, L["gu_w"], None)
-            return self._lin(li, "down", act, L["down_w"], residual=x)
+            _, act, _ = self._gu_fwd(li, h, L["gu_w"], None, i8=i8("gu_w"))
+            return self._lin(li, "down", act, L["down_w"], residual=x, i8=i8("down_w"))
         x = hk.gemm_nt(o, L["o_w"], residual=x)
         h = hk.rmsnorm_fwd(x, L["ln2_w"], self.eps, out=h)
         act = hk.swiglu_fwd(hk.gemm_nt(h, L["gu_w"]), ff)
@@ -814,6 +817,17 @@ class TextModal:
                 codes, scales = hk.quant_mx4_rows(L[k])
                 L[k + "mx4"] = hk.repack_mx4_mfma(codes, scales)
                 del codes, scales
+
+    def pack_int8_decode(self):
+        """Decode-only copies of the int8 rows of the LLM.int8 base in the operand order of `hk.gemv_int8` (`hk.repack_int8_mfma`), under
+        `L[name + "i8p"]` (+6.7 GB at full depth next to the row-major rows that the prefill and training products read): the single-token
+        weight stream then reads consecutive 1-KiB lines.  The codes are the base's own; nothing is quantised anew.  lm_head is not
+        quantised in the reference and has no int8 form."""
+        if not self.p["layers"] or "qkv_wi8" not in self.p["layers"][0]:
+            raise ValueError('pack_int8_decode: the decoder is not on the LLM.int8 base - call quantize_base(8, "int8") first')
+        for L in self.p["layers"]:
+            for k in ("qkv_w", "o_w", "gu_w", "down_w"):
+                L[k + "i8p"] = hk.repack_int8_mfma(L[k + "i8"])
 
     def quantize_base(self, bits: int = 8, scheme: str = "e4m3", quant_type: str = "nf4", double_quant: bool = True):
         """`bits: 8` of Config/multi_modal_stage{2,3}.yaml (text_modal.py:91-131: the reference loads the frozen LLaMA through bitsandbytes
@@ -932,9 +946,17 @@ class TextModal:
         s.pos = torch.zeros(B, device=dev, dtype=torch.int32)
         scale = 1.0 / math.sqrt(hd)
 
-        if weights not in ("bf16", "fp8", "4bit", "mxfp4"):
-            raise ValueError(f"weights={weights!r}: expected 'bf16', 'fp8', '4bit' or 'mxfp4'")
-        fp8, w4, mx4 = weights == "fp8", weights == "4bit", weights == "mxfp4"
+        if weights not in ("bf16", "fp8", "4bit", "mxfp4", "int8"):
+            raise ValueError(f"weights={weights!r}: expected 'bf16', 'fp8', '4bit', 'mxfp4' or 'int8'")
+        fp8, w4, mx4, w8i = weights == "fp8", weights == "4bit", weights == "mxfp4", weights == "int8"
+        if w8i:  # the decoder linears stream the int8 rows of the LLM.int8 base (hk.int8_decode_prepare + hk.gemv_int8); lm_head stays bf16
+            if "qkv_wi8" not in self.p["layers"][0]:
+                raise ValueError('weights="int8" needs the LLM.int8 base: quantize_base(8, "int8") (YAML `bits: 8`)')
+            if d % 64 or ff % 64 or max(d, ff) > 16384:
+                raise ValueError(f'weights="int8" needs hidden sizes that are multiples of 64 (the MFMA step) and at most 16384, got {d} and {ff}')
+            if "qkv_wi8p" not in self.p["layers"][0]:
+                self.pack_int8_decode()
+            s.i8ws = hk.Int8DecodeWorkspace(dev, B, max(d, ff), self._i8ws.threshold if self._i8ws is not None else 6.0)
         if fp8 and "qkv_w8p" not in self.p["layers"][0]:
             self.pack_fp8_decode()
         if w4:  # the decoder linears stream the 4-bit codes (hk.gemv4); lm_head is not quantised in the reference and stays bf16
@@ -949,7 +971,7 @@ class TextModal:
                 self.pack_mx4_decode()
 
         packed16 = not fp8 and B >= 2 and d % 128 == 0 and ff % 128 == 0  # batched bf16: the MFMA GEMV on re-tiled weights
-        if packed16 and (w4 or mx4):  # lm_head alone: pack_bf16_decode() would add 13.5 GB of re-tiled decoder weights that this mode never reads
+        if packed16 and (w4 or mx4 or w8i):  # lm_head alone: pack_bf16_decode() would add 13.5 GB of re-tiled decoder weights that this mode never reads
             if "lm_headp" not in self.p:
                 self.p["lm_headp"] = hk.repack_bf16_mfma(self.p["lm_head"])
         elif packed16 and "qkv_wp" not in self.p["layers"][0]:
@@ -960,6 +982,8 @@ class TextModal:
                 return L[name + "4p"], None
             if mx4:
                 return L[name + "mx4"], None
+            if w8i:
+                return L[name + "i8p"], L[name + "i8s"]
             return (L[name + "8p"], L[name + "8s"]) if fp8 else (L[name + "p"] if packed16 else L[name], None)
 
         # the MFMA weight streams (bf16 and 4-bit alike) read x from L2 with prologue 0: norm / SwiGLU run once, not once per block (pays from batch 4)
@@ -1007,6 +1031,10 @@ class TextModal:
                 else:
                     q = hk.quant_fp8_rows(x_in, out=s.x8 if K == d else s.a8)   # K = ff: the materialised SwiGLU of the batched live-adapter path
                 hk.gemv_mx4(w, q[0], q[1], out, residual=residual, out_f32=out_f32)
+                return
+            if isinstance(w, hk.PackedI8):   # prologue, outlier split and quantisation in one launch, then the int8 weight stream
+                hk.int8_decode_prepare(x_in, K, s.i8ws, prologue=pro, norm_w=norm_w, eps=self.eps)
+                hk.gemv_int8(w, sc, s.i8ws, out, K, residual=residual, out_f32=out_f32)
                 return
             x_in, pro, norm_w = staged(x_in, pro, norm_w)
             if isinstance(w, hk.Packed4):
@@ -1116,7 +1144,12 @@ class TextModal:
         "mxfp4" - on any base: the decoder linears stream OCP MXFP4 copies (e2m1 codes + one e8m0 scale per 32 k, 0.53 B per weight, made by
         `pack_mx4_decode` from whatever bf16 weights the decoder holds at the first call - merged copies included) against per-row e4m3
         activations, dequantised and multiplied by the block-scaled MFMA itself (`hk.gemv_mx4`).  Lossy like "fp8" (the weights are rounded to
-        4 bits); lm_head stays bf16, and the prefill stays on the bf16 GEMMs in every mode.
+        4 bits); lm_head stays bf16, and the prefill stays on the bf16 GEMMs in every mode but "int8".
+        "int8" - only on the LLM.int8 base (`quantize_base(8, "int8")`, else ValueError): the decoder linears stream the base's own int8 rows
+        and row factors (1 B per weight, re-tiled once by `pack_int8_decode`) in the arithmetic of bitsandbytes' MatMul8bitLt - per linear
+        `hk.int8_decode_prepare` (prologue, outlier columns >= 6.0, per-row int8 codes) and `hk.gemv_int8` (exact int32 product on the int8
+        MFMA + the 16-bit outlier columns) -, and the prefill and the batch > 16 step run `hk.int8_linear`, so the whole call computes what the
+        reference's `generate` computes on a `load_in_8bit` model.  lm_head stays bf16.  With un-merged adapters it needs `adapters="live"`.
 
         `kv_cache`: "bf16" (default) or "fp8" - the K / V caches hold e4m3 codes and one e8m0 scale byte per head row (the kv8 format of
         csrc/decode_kv8.hip: half the cache memory, half the cache stream of a step and of a beam reorder).  The prefill attends over the exact
@@ -1140,6 +1173,8 @@ class TextModal:
                   eos_token_id=eos_token_id, return_logits=return_logits, use_graph=use_graph, weights=weights, sampler=sampler, seed=seed,
                   repetition_penalty=repetition_penalty, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
                   return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1), kv_cache=kv_cache)
+        if weights == "int8" and not self.base_int8:
+            raise ValueError('weights="int8" needs the LLM.int8 base: quantize_base(8, "int8") (YAML `bits: 8`)')
         if self.lora is None:
             return self._generate(input_ids, **kw)
         if adapters == "live":   # nothing is merged or swapped: the bf16 base weights serve prefill, `weights` picks the decode stream, dropout is off
@@ -1154,6 +1189,10 @@ class TextModal:
             raise ValueError('weights="4bit" with un-merged LoRA adapters: generate() then runs on merged 16-bit COPIES, which have no 4-bit form - '
                              'call merge_lora() first (it re-quantises the merged weights, as peft does for a merged Linear4bit), or pass '
                              'adapters="live" (the adapters then run next to the 4-bit codes)')
+        if weights == "int8":
+            raise ValueError('weights="int8" with un-merged LoRA adapters: generate() then runs on merged 16-bit COPIES, which have no int8 form - '
+                             'call merge_lora() first (it re-quantises the merged weights), or pass adapters="live" (the adapters then run '
+                             'next to the int8 rows)')
         base_layers, base8, base_i8 = self.p["layers"], self.base8, self.base_int8
         self.p["layers"], self.base8, self.base_int8 = self._lora_merged_layers(), False, False   # merged 16-bit copies: no 8-bit operands of them exist
         try:
@@ -1208,6 +1247,7 @@ class TextModal:
         caches = self._alloc_kv(B * max_ctx, kv_cache)
 
         lora = self.lora if live_lora else None   # adapters="live": the store the session and the GEMM steps read
+        w8i = weights == "int8"                   # prefill and the batch > 16 step run the LLM.int8 products too: the whole call is in that arithmetic
         s, seen, step_dev = None, None, None
         if device_pick:
             seed = int(torch.initial_seed() if seed is None else seed)
@@ -1234,7 +1274,7 @@ class TextModal:
         desc = hk.make_desc([(b * S0, S0, b * (S0 if kv_cache == "fp8" else max_ctx), S0, S0, 0) for b in range(B)], dev)
         x = embeds.reshape(B * S0, d)
         for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
-            x = self._layer_step(L, x, B, S0, 0, cache, desc, max_ctx, kmask, li=li if lora is not None else None)
+            x = self._layer_step(L, x, B, S0, 0, cache, desc, max_ctx, kmask, li=li if lora is not None or w8i else None, int8=w8i)
         hn = hk.rmsnorm_fwd(x.view(B, S0, d)[:, -1].contiguous(), self.p["norm_w"], self.eps)
         logits = hk.gemm_nt(hn, self.p["lm_head"], out_f32=True)  # [B, V] fp32 (HF: logits.float())
         all_logits = [logits.clone()] if return_logits else []
@@ -1302,7 +1342,7 @@ class TextModal:
                 x = hk.gather_rows(self.p["embed"], out_ids[-1].clamp(0, self.vocab - 1).to(torch.int32))
                 desc = hk.make_desc([(b, 1, b * max_ctx, ctx + 1, ctx + 1, ctx) for b in range(B)], dev)
                 for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
-                    x = self._layer_step(L, x, B, 1, ctx, cache, desc, max_ctx, kmask, li=li if lora is not None else None)
+                    x = self._layer_step(L, x, B, 1, ctx, cache, desc, max_ctx, kmask, li=li if lora is not None or w8i else None, int8=w8i)
                 logits = hk.gemm_nt(hk.rmsnorm_fwd(x, self.p["norm_w"], self.eps), self.p["lm_head"], out_f32=True)
                 if return_logits:
                     all_logits.append(logits.clone())
@@ -1360,6 +1400,7 @@ class TextModal:
         kv8 = kv_cache == "fp8"
         caches = self._alloc_kv(R * max_ctx, kv_cache)
         lora = self.lora if live_lora else None
+        w8i = weights == "int8"
         s = self._decode_session(R, max_ctx, caches, max_new_tokens, weights, kmask_r, lora, kv_cache)
         s.state[0], s.state[1] = S0, 0
         st = hk.BeamState(B, nb, V, max_new_tokens, length_penalty, dev)
@@ -1374,7 +1415,7 @@ class TextModal:
         desc = hk.make_desc([(b * S0, S0, b * (S0 if kv8 else nb * max_ctx), S0, S0, 0) for b in range(B)], dev)
         x = embeds.reshape(B * S0, d)
         for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
-            x = self._layer_step(L, x, B, S0, 0, cache, desc, nb * max_ctx, kmask, li=li if lora is not None else None)
+            x = self._layer_step(L, x, B, S0, 0, cache, desc, nb * max_ctx, kmask, li=li if lora is not None or w8i else None, int8=w8i)
         hn = hk.rmsnorm_fwd(x.view(B, S0, d)[:, -1].contiguous(), self.p["norm_w"], self.eps)
         logits = hk.gemm_nt(hn, self.p["lm_head"], out_f32=True).repeat_interleave(nb, 0).contiguous()   # the row's beams all start from it
         all_logits = [logits] if return_logits else []

@@ -12,6 +12,9 @@
                                                                                  `bf16` then streams the dequantised weights: same bytes, same speed
     python tools/decode_bench.py 256 bf16,fp8,mxfp4 1 --repeats 3                the same with the MXFP4 decode copies (any base; generate builds them
                                                                                  at the warm-up call)
+    python tools/decode_bench.py 256 bf16,fp8,int8 1 --repeats 3                 the same with the int8 rows of the LLM.int8 base: with `int8` in the
+                                                                                 list the model is put on quantize_base(8, "int8") before the warm-up;
+                                                                                 `bf16` then streams the dequantised weights and `fp8` e4m3 copies of them
     python tools/decode_bench.py 256 bf16,4bit 1 --lora-r 8 --lora-targets q,k,v,o --adapters merged,live --repeats 3
                                                                                  un-merged LoRA adapters (random, non-zero B): generate(adapters=...)
                                                                                  modes alternate inside every repeat.  Each mode's FIRST call starts
@@ -44,7 +47,8 @@ ap.add_argument("--kv-cache", default="bf16", help="bf16 | fp8 | a comma list th
 a = ap.parse_args()
 new, B = a.new, a.batch
 weight_modes = a.weights.split(",")
-assert all(w in ("bf16", "fp8", "4bit", "mxfp4") for w in weight_modes), a.weights
+assert all(w in ("bf16", "fp8", "4bit", "mxfp4", "int8") for w in weight_modes), a.weights
+assert not ("4bit" in weight_modes and "int8" in weight_modes), "4bit and int8 need different bases: one run each"
 model = UniBind(("rgb", "text"), None, device="cuda", llama_layers=a.layers).init_random(seed=0).eval()
 ids = torch.randint(3, 32000, (B, 60)); ids[:, 0] = 1; ids[:, 1] = -200
 rgb = torch.randn(B, 3, 224, 224)
@@ -53,6 +57,8 @@ assert all(m in ("off", "torch", "device", "beam", "rows") for m in modes), a.sa
 ids_rows, rgb_rows = ids.repeat(a.num_beams, 1), rgb.repeat(a.num_beams, 1, 1, 1)   # mode `rows`: the prompt N times
 if "4bit" in weight_modes:
     model.text.quantize_base(4, quant_type="nf4", double_quant=True)
+if "int8" in weight_modes:
+    model.text.quantize_base(8, "int8")
 adapter_modes = a.adapters.split(",") if a.lora_r > 0 else [None]
 assert all(m in ("merged", "live", None) for m in adapter_modes), a.adapters
 kv_modes = a.kv_cache.split(",")
@@ -87,6 +93,16 @@ def token_bytes_mxfp4():
     for L in model.text.p["layers"]:
         for k in ("qkv_w", "o_w", "gu_w", "down_w"):
             total += L[k + "mx4"].nbytes()
+    return total
+
+
+def token_bytes_int8():
+    """bytes of weights one `int8` token streams, from the tensors generate() reads: the tiled int8 rows (padding rows included) and fp32 row
+    factors of every decoder linear, and the bf16 lm_head"""
+    total = model.text.p["lm_head"].numel() * model.text.p["lm_head"].element_size()
+    for L in model.text.p["layers"]:
+        for k in ("qkv_w", "o_w", "gu_w", "down_w"):
+            total += L[k + "i8p"].nbytes() + L[k + "i8s"].numel() * L[k + "i8s"].element_size()
     return total
 
 
@@ -130,8 +146,8 @@ runs = []
 for mode in modes:
     for weights in weight_modes:
         for ad in adapter_modes:
-            if ad == "merged" and weights == "4bit":
-                print(f"[{weights}, batch {B}, adapters merged] n/a: raises (merged 16-bit copies have no 4-bit form)", flush=True)
+            if ad == "merged" and weights in ("4bit", "int8"):
+                print(f"[{weights}, batch {B}, adapters merged] n/a: raises (merged 16-bit copies have no {weights} form)", flush=True)
                 continue
             for kvc in kv_modes:
                 runs.append((mode, weights, ad, kvc))
@@ -164,6 +180,11 @@ if "4bit" in weight_modes:
 if "mxfp4" in weight_modes and "qkv_wmx4" in model.text.p["layers"][0]:   # with adapters="merged" the copies hang on the merged layers instead
     gb = token_bytes_mxfp4() / 1e9
     roofline["mxfp4"] = f"{gb:.3g} GB/token @ 8 TB/s = {8000 / gb:.0f} tok/s"
+if "int8" in weight_modes and "qkv_wi8p" in model.text.p["layers"][0]:
+    gb = token_bytes_int8() / 1e9
+    roofline["int8"] = f"{gb:.3g} GB/token @ 8 TB/s = {8000 / gb:.0f} tok/s"
+if "int8" in weight_modes:
+    roofline.setdefault("int8", "n/a (the tiled int8 rows belong to no layer: every int8 run raised)")
 roofline.setdefault("mxfp4", "n/a (the MXFP4 copies belong to the merged layers)")
 for _ in range(a.repeats):
     for mode, weights, ad, kvc in runs:
