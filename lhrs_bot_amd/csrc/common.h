@@ -115,6 +115,14 @@ __device__ __forceinline__ void unpack8(const uint4& u, float (&v)[8]) {
 __device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
   return make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
 }
+// eight fp32 values times inv -> eight OCP e4m3 bytes (RNE, saturating), in memory order
+__device__ __forceinline__ int2 cvt8_e4m3(const float (&v)[8], float inv) {
+  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, 0, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, lo, true);
+  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, 0, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, hi, true);
+  return make_int2(lo, hi);
+}
 // LoRA dropout (peft lora.Linear: lora_B(lora_A(dropout(x))), p = 0.05 in Config/multi_modal_stage2.yaml): counter-based mask - element
 // idx of the adapter INPUT is kept iff lowbias32(idx, seed) >= p * 2^32 - so forward, backward and the tests regenerate the same mask
 __device__ __forceinline__ bool drop_keep(unsigned seed, long idx, unsigned thresh) {
@@ -125,3 +133,4 @@ __device__ __forceinline__ bool drop_keep(unsigned seed, long idx, unsigned thre
 __device__ __forceinline__ float silu(float x) { return x * sigmoid_f(x); }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }  // 16-B lane loads

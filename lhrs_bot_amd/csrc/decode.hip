@@ -7,14 +7,13 @@
 //   decode_advance: bumps the device-resident context length and rewrites the attention descriptor / rope position so
 //                   that ONE captured hipGraph replays for every token (no kernel argument changes between tokens).
 //   kv_append     : writes the new K / V rows at position ctx of the cache.
-#include "common.h"
+#include "decode_linear.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
-// PRO: what the block does to the activation rows while staging them in LDS (every block redoes it: 8-22 KB from L2)
-//   0 plain copy            1 RMSNorm (HF LlamaRMSNorm: w * bf16(x * rsqrt(mean x^2 + eps)))       2 SwiGLU: silu(x[k]) * x[K + k]
+// PRO: what the block does to the activation rows while staging them in LDS (stage_x of decode_linear.h)
 // FP8: W is OCP e4m3 with one fp32 scale per output row (the 6.7 GB / token weight stream of SURVEY.md §8d)
 // RPW rows per wave; UNR 1-KiB row chunks per lane-iteration (bf16 weights): RPW * UNR 16-B loads per lane are prefetched one iteration
 // ahead, so a wave keeps RPW * UNR .. 2 * RPW * UNR KiB in flight.  The per-row summation order does not depend on RPW / UNR.
@@ -40,34 +39,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ Wv, 
         wcur[u][r] = make_uint4((unsigned)t[0], (unsigned)t[1], (unsigned)t[2], (unsigned)t[3]);
       }
   }
-  for (int b = 0; b < NB; ++b) {
-    if (PRO == 2) {
-      for (int c = tid; c < nch; c += 256) {
-        const uint4 g = *reinterpret_cast<const uint4*>(x + b * ldx + c * 8);
-        const uint4 u = *reinterpret_cast<const uint4*>(x + b * ldx + K + c * 8);
-        uint4 o;
-        o.x = pack2bf(silu(bflo(g.x)) * bflo(u.x), silu(bfhi(g.x)) * bfhi(u.x));
-        o.y = pack2bf(silu(bflo(g.y)) * bflo(u.y), silu(bfhi(g.y)) * bfhi(u.y));
-        o.z = pack2bf(silu(bflo(g.z)) * bflo(u.z), silu(bfhi(g.z)) * bfhi(u.z));
-        o.w = pack2bf(silu(bflo(g.w)) * bflo(u.w), silu(bfhi(g.w)) * bfhi(u.w));
-        *reinterpret_cast<uint4*>(xs + b * K + c * 8) = o;
-      }
-    } else {
-      float q = 0.f;
-      for (int c = tid; c < nch; c += 256) {
-        const uint4 v = *reinterpret_cast<const uint4*>(x + b * ldx + c * 8);
-        *reinterpret_cast<uint4*>(xs + b * K + c * 8) = v;
-        if (PRO == 1)
-          q += bflo(v.x) * bflo(v.x) + bfhi(v.x) * bfhi(v.x) + bflo(v.y) * bflo(v.y) + bfhi(v.y) * bfhi(v.y) + bflo(v.z) * bflo(v.z) +
-               bfhi(v.z) * bfhi(v.z) + bflo(v.w) * bflo(v.w) + bfhi(v.w) * bfhi(v.w);
-      }
-      if (PRO == 1) {
-        const float rstd = rsqrtf(block_sum<4>(q, red) / (float)K + eps);
-        __syncthreads();
-        for (int c = tid; c < K; c += 256) xs[b * K + c] = f2bf(bf2f(norm_w[c]) * bf2f(f2bf(bf2f(xs[b * K + c]) * rstd)));
-      }
-    }
-  }
+  stage_x<PRO, 256>(x, ldx, norm_w, eps, xs, red, NB, K);
   __syncthreads();
   float acc[RPW][NB];
 #pragma unroll
@@ -144,12 +116,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ Wv, 
     for (int b = 0; b < NB; ++b) {
       const float s = wave_sum(acc[r][b]);
       const int row = row0 + r;
-      if (lane == 0 && row < N) {
-        float v = FP8 ? s * wscale[row] : s;
-        if (res) v += bf2f(res[b * ldr + row]);
-        if (out_f32) reinterpret_cast<float*>(y)[b * ldy + row] = v;
-        else reinterpret_cast<bf16_t*>(y)[b * ldy + row] = f2bf(v);
-      }
+      if (lane == 0 && row < N) store_y(y, out_f32, b, ldy, row, FP8 ? s * wscale[row] : s, res, ldr);
     }
 }
 
@@ -173,9 +140,8 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_kernel(const bf16_t* __rest
   __shared__ float part[NW][16][17];
   bf16_t* xs = reinterpret_cast<bf16_t*>(smem);  // [NB][K]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
-  const int nch = K / 8;
   const int row0 = blockIdx.x * 16;
-  const int kq = K / NW;                     // this wave's slice of K (K % (32 NW) == 0)
+  const int kq = K / NW;                    // this wave's slice of K (K % (32 NW) == 0)
   const bf16_t* wp = PK ? W + ((long)blockIdx.x * (K / 32) + wave * (kq / 32)) * 512 + lane * 8
                         : W + (long)min(row0 + fr, N - 1) * ldw + wave * kq + fg * 8;
   constexpr int WSTEP = PK ? 512 : 32;       // elements between consecutive 32-k steps of this lane
@@ -184,34 +150,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_kernel(const bf16_t* __rest
   const int nsteps = kq / 32;                // 1 (K 128 at 4 waves, K 256 at 8) or more: the preload stays inside the wave's own slice
 #pragma unroll
   for (int u = 0; u < U; ++u) wreg[u] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(wp + (long)min(u, nsteps - 1) * WSTEP));
-  for (int b = 0; b < (PRO == 0 ? 0 : NB); ++b) {  // PRO 0: x is read straight from L2 into the B fragments, nothing to stage
-    if (PRO == 2) {
-      for (int c = tid; c < nch; c += NW * 64) {
-        const uint4 g = *reinterpret_cast<const uint4*>(x + b * ldx + c * 8);
-        const uint4 u = *reinterpret_cast<const uint4*>(x + b * ldx + K + c * 8);
-        uint4 o;
-        o.x = pack2bf(silu(bflo(g.x)) * bflo(u.x), silu(bfhi(g.x)) * bfhi(u.x));
-        o.y = pack2bf(silu(bflo(g.y)) * bflo(u.y), silu(bfhi(g.y)) * bfhi(u.y));
-        o.z = pack2bf(silu(bflo(g.z)) * bflo(u.z), silu(bfhi(g.z)) * bfhi(u.z));
-        o.w = pack2bf(silu(bflo(g.w)) * bflo(u.w), silu(bfhi(g.w)) * bfhi(u.w));
-        *reinterpret_cast<uint4*>(xs + b * K + c * 8) = o;
-      }
-    } else {
-      float q = 0.f;
-      for (int c = tid; c < nch; c += NW * 64) {
-        const uint4 v = *reinterpret_cast<const uint4*>(x + b * ldx + c * 8);
-        *reinterpret_cast<uint4*>(xs + b * K + c * 8) = v;
-        if (PRO == 1)
-          q += bflo(v.x) * bflo(v.x) + bfhi(v.x) * bfhi(v.x) + bflo(v.y) * bflo(v.y) + bfhi(v.y) * bfhi(v.y) + bflo(v.z) * bflo(v.z) +
-               bfhi(v.z) * bfhi(v.z) + bflo(v.w) * bflo(v.w) + bfhi(v.w) * bfhi(v.w);
-      }
-      if (PRO == 1) {
-        const float rstd = rsqrtf(block_sum<NW>(q, red) / (float)K + eps);
-        __syncthreads();
-        for (int c = tid; c < K; c += NW * 64) xs[b * K + c] = f2bf(bf2f(norm_w[c]) * bf2f(f2bf(bf2f(xs[b * K + c]) * rstd)));
-      }
-    }
-  }
+  if (PRO != 0) stage_x<PRO, NW * 64>(x, ldx, norm_w, eps, xs, red, NB, K);  // PRO 0: x is read straight from L2 into the B fragments
   __syncthreads();
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const bf16_t* xq = (PRO == 0 ? x + (long)min(fr, NB - 1) * ldx : xs + (long)min(fr, NB - 1) * K) + wave * kq + fg * 8;
@@ -236,20 +175,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_kernel(const bf16_t* __rest
 #pragma unroll
     for (int u = 0; u < U; ++u) wreg[u] = wnext[u];
   }
-  // acc[r] = partial y[batch = fr][row0 + 4*fg + r] of this wave's K quarter
-#pragma unroll
-  for (int r = 0; r < 4; ++r) part[wave][fg * 4 + r][fr] = acc[r];
-  __syncthreads();
-  const int i = tid >> 4, b = tid & 15;  // the first 256 threads = 16 rows x 16 batch columns
-  const int row = row0 + i;
-  if (tid < 256 && b < NB && row < N) {
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) v += part[w][i][b];
-    if (res) v += bf2f(res[b * ldr + row]);
-    if (out_f32) reinterpret_cast<float*>(y)[b * ldy + row] = v;
-    else reinterpret_cast<bf16_t*>(y)[b * ldy + row] = f2bf(v);
-  }
+  mfma_tile_store<NW, 0>(part, acc, wave, fr, fg, row0, NB, N, nullptr, nullptr, res, ldr, y, ldy, out_f32);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -264,24 +190,23 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_kernel(const bf16_t* __rest
 // and a 4096-B row stride additionally camps on few channels; the tiled stream matches the bf16 GEMV's contiguous rows).
 // ------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
-constexpr int GF_WAVES = 8, GF_THREADS = GF_WAVES * 64, GF_MAXC = 3;  // fused prologue: K <= GF_THREADS * GF_MAXC * 8 = 12288
 
 // PRO < 0: x8 / xscale come from global memory (already quantised; any batch <= 16).
 // PRO 0 / 1 / 2 (batch <= 2): x is bf16; the block applies the prologue (copy / RMSNorm / SwiGLU) AND the per-row e4m3 quantisation
-// itself while the first weight lines are in flight - the row stays in registers between the reductions, only the e4m3 bytes go to
-// LDS.  Every block recomputes the same few KB, which keeps the decode step at five launches per layer.
+// itself while the first weight lines are in flight (stage_x_e4m3 of decode_linear.h, whose block of QX_WAVES waves this kernel has).
+// Every block recomputes the same few KB, which keeps the decode step at five launches per layer.
 template <int PRO, bool PK>
-__global__ __launch_bounds__(GF_THREADS) void gemv_fp8_mfma_kernel(const uint8_t* __restrict__ W, long ldw, const float* __restrict__ wscale,
+__global__ __launch_bounds__(QX_THREADS) void gemv_fp8_mfma_kernel(const uint8_t* __restrict__ W, long ldw, const float* __restrict__ wscale,
                                                                    const void* __restrict__ xin, long ldx, const float* __restrict__ xscale,
                                                                    const bf16_t* __restrict__ norm_w, float eps, const bf16_t* res, long ldr,
                                                                    void* y, long ldy, int NB, int N, int K, int out_f32) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // PRO >= 0: [NB][K] e4m3 bytes
-  __shared__ float part[GF_WAVES][16][17];
-  __shared__ float red[GF_WAVES];
+  __shared__ float part[QX_WAVES][16][17];
+  __shared__ float red[QX_WAVES];
   __shared__ float s_scale[2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
   const int row0 = blockIdx.x * 16;
-  const int nsteps = K / 128, per = (nsteps + GF_WAVES - 1) / GF_WAVES;
+  const int nsteps = K / 128, per = (nsteps + QX_WAVES - 1) / QX_WAVES;
   const int s_begin = min(wave * per, nsteps), s_end = min(nsteps, s_begin + per);
   const uint8_t* wp = PK ? W + (long)blockIdx.x * nsteps * 2048 + lane * 16 : W + (long)min(row0 + fr, N - 1) * ldw + fg * 16;
   constexpr long WSTEP = PK ? 2048 : 128, WHALF = PK ? 1024 : 64;
@@ -296,64 +221,7 @@ __global__ __launch_bounds__(GF_THREADS) void gemv_fp8_mfma_kernel(const uint8_t
   const uint8_t* xp;
   if (PRO >= 0) {
     uint8_t* x8s = reinterpret_cast<uint8_t*>(smem);
-    const bf16_t* x = reinterpret_cast<const bf16_t*>(xin);
-    const int nch = K / 8;
-    for (int b = 0; b < NB; ++b) {
-      float v[GF_MAXC][8], g[GF_MAXC][8];
-      float q = 0.f;
-#pragma unroll
-      for (int i = 0; i < GF_MAXC; ++i) {
-        const int c = tid + i * GF_THREADS;
-        if (c < nch) {
-          uint4 t = *reinterpret_cast<const uint4*>(x + b * ldx + c * 8);
-          if (PRO == 2) {
-            const uint4 u = *reinterpret_cast<const uint4*>(x + b * ldx + K + c * 8);
-            t.x = pack2bf(silu(bflo(t.x)) * bflo(u.x), silu(bfhi(t.x)) * bfhi(u.x));
-            t.y = pack2bf(silu(bflo(t.y)) * bflo(u.y), silu(bfhi(t.y)) * bfhi(u.y));
-            t.z = pack2bf(silu(bflo(t.z)) * bflo(u.z), silu(bfhi(t.z)) * bfhi(u.z));
-            t.w = pack2bf(silu(bflo(t.w)) * bflo(u.w), silu(bfhi(t.w)) * bfhi(u.w));
-          }
-          unpack8(t, v[i]);
-          if (PRO == 1) {
-            unpack8(*reinterpret_cast<const uint4*>(norm_w + c * 8), g[i]);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) q += v[i][e] * v[i][e];
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[i][e] = 0.f;
-        }
-      }
-      if (PRO == 1) {
-        const float rstd = rsqrtf(block_sum<GF_WAVES>(q, red) / (float)K + eps);
-#pragma unroll
-        for (int i = 0; i < GF_MAXC; ++i)
-          if (tid + i * GF_THREADS < nch) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[i][e] = bf2f(f2bf(g[i][e] * bf2f(f2bf(v[i][e] * rstd))));  // HF LlamaRMSNorm roundings
-          }
-      }
-      float m = 0.f;
-#pragma unroll
-      for (int i = 0; i < GF_MAXC; ++i)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(v[i][e]));
-      m = block_max<GF_WAVES>(m, red);
-      const float sc = m > 0.f ? m / 448.f : 1.f;
-      if (tid == 0) s_scale[b] = sc;
-      const float inv = 1.f / sc;
-#pragma unroll
-      for (int i = 0; i < GF_MAXC; ++i) {
-        const int c = tid + i * GF_THREADS;
-        if (c < nch) {
-          int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][0] * inv, v[i][1] * inv, 0, false);
-          lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][2] * inv, v[i][3] * inv, lo, true);
-          int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][4] * inv, v[i][5] * inv, 0, false);
-          hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][6] * inv, v[i][7] * inv, hi, true);
-          *reinterpret_cast<int2*>(x8s + (size_t)b * K + c * 8) = make_int2(lo, hi);
-        }
-      }
-    }
+    stage_x_e4m3<PRO>(reinterpret_cast<const bf16_t*>(xin), ldx, norm_w, eps, x8s, red, s_scale, NB, K);
     __syncthreads();
     xp = x8s + (size_t)min(fr, NB - 1) * K + fg * 16;
   } else {
@@ -392,21 +260,7 @@ __global__ __launch_bounds__(GF_THREADS) void gemv_fp8_mfma_kernel(const uint8_t
       for (int u = 0; u < U; ++u) { wlo[u] = wnlo[u]; whi[u] = wnhi[u]; }
     }
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) part[wave][fg * 4 + r][fr] = acc[r];
-  __syncthreads();
-  const int i = tid >> 4, b = tid & 15;
-  const int row = row0 + i;
-  if (tid < 256 && b < NB && row < N) {
-    const float xs_b = PRO >= 0 ? s_scale[b] : xscale[b];
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < GF_WAVES; ++w) v += part[w][i][b];
-    v *= wscale[row] * xs_b;
-    if (res) v += bf2f(res[b * ldr + row]);
-    if (out_f32) reinterpret_cast<float*>(y)[b * ldy + row] = v;
-    else reinterpret_cast<bf16_t*>(y)[b * ldy + row] = f2bf(v);
-  }
+  mfma_tile_store<QX_WAVES, 2>(part, acc, wave, fr, fg, row0, NB, N, wscale, PRO >= 0 ? s_scale : xscale, res, ldr, y, ldy, out_f32);
 }
 
 // e4m3 [N, ldw] rows -> the tiled operand order of gemv_fp8_mfma_kernel<*, true>: piece p = ((rg * K/128 + step) * 2 + half) * 64 + lane
@@ -478,11 +332,7 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __res
   auto cvt8 = [&](const uint4& raw, int c) {
     float v[8];
     unpack8(raw, v);
-    int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, 0, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, lo, true);
-    int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, 0, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, hi, true);
-    *reinterpret_cast<int2*>(orow + c * 8) = make_int2(lo, hi);
+    *reinterpret_cast<int2*>(orow + c * 8) = cvt8_e4m3(v, inv);
   };
 #pragma unroll
   for (int i = 0; i < QCH; ++i) {
@@ -979,12 +829,9 @@ extern "C" int lhrs_gemv(const void* W, long ldw, const float* wscale, int w_for
   LHRS_REQUIRE(B <= 8 || (!w_fp8 && K % 128 == 0), "gemv: batches above 8 need bf16 weights and K %% 128 == 0");
   LHRS_REQUIRE(w_fp8 ? (ldw % 16 == 0 && wscale != nullptr) : (w_packed || ldw % 8 == 0), "gemv: weight stride / scales");
   LHRS_REQUIRE(prologue >= 0 && prologue <= 2 && (prologue != 1 || norm_w != nullptr), "gemv: prologue %d", prologue);
-  // staged activations: 152 KiB, and together with the static LDS of the kernel the chunk goes to (the MFMA kernel's part[NW][16][17] +
-  // red[NW] = 8736 B at 8 waves, 4368 B at 4) no more than the 160 KiB of a CU
+  // static LDS of the kernel the chunk goes to: the MFMA kernel's part[NW][16][17] + red[NW] = 8736 B at 8 waves, 4368 B at 4
   const bool mfma = !w_fp8 && B >= 2 && K % 128 == 0;
-  const long lds_static = mfma ? (K % 256 == 0 ? 8 : 4) * (16 * 17 + 1) * 4L : 16;
-  const long lds_x = 152L * 1024 < 160L * 1024 - lds_static ? 152L * 1024 : 160L * 1024 - lds_static;
-  int bmax = (int)(lds_x / ((long)K * 2));
+  int bmax = staged_rows_max(K, mfma ? (K % 256 == 0 ? 8 : 4) * (16 * 17 + 1) * 4L : 16);
   if (mfma && prologue == 0) bmax = 16;  // the MFMA kernel reads x from L2: no LDS limit
   LHRS_REQUIRE(bmax >= 1, "gemv: one activation vector does not fit LDS (K=%d)", K);
   const long esz = out_f32 ? 4 : 2;
@@ -1143,7 +990,7 @@ extern "C" int lhrs_gemv_fp8_mfma(const void* W8, long ldw, const float* wscale,
   LHRS_REQUIRE(B >= 1 && B <= 16 && N > 0 && K >= 128 && K % 128 == 0, "gemv_fp8_mfma: B=%d N=%d K=%d", B, N, K);
   LHRS_REQUIRE((w_packed || ldw % 16 == 0) && ldx % 16 == 0 && wscale && xscale, "gemv_fp8_mfma: strides / scales");
 #define GOP(PK)                                                                                                                      \
-  hipLaunchKernelGGL((gemv_fp8_mfma_kernel<-1, PK>), dim3(cdiv(N, 16)), dim3(GF_THREADS), 0, (hipStream_t)stream, (const uint8_t*)W8, ldw, \
+  hipLaunchKernelGGL((gemv_fp8_mfma_kernel<-1, PK>), dim3(cdiv(N, 16)), dim3(QX_THREADS), 0, (hipStream_t)stream, (const uint8_t*)W8, ldw, \
                      wscale, x8, ldx, xscale, (const bf16_t*)nullptr, 0.f, (const bf16_t*)residual, ldr, y, ldy, B, N, K, out_f32)
   if (w_packed) GOP(true); else GOP(false);
 #undef GOP
@@ -1159,9 +1006,9 @@ extern "C" int lhrs_gemv_fp8_mfma_fused(const void* W8, long ldw, const float* w
   LHRS_REQUIRE(B >= 1 && B <= 2 && N > 0 && K >= 128 && K % 128 == 0, "gemv_fp8_mfma_fused: B=%d (1..2) N=%d K=%d", B, N, K);
   LHRS_REQUIRE((w_packed || ldw % 16 == 0) && ldx % 8 == 0 && wscale && prologue >= 0 && prologue <= 2 && (prologue != 1 || norm_w),
                "gemv_fp8_mfma_fused: args");
-  LHRS_REQUIRE(K <= GF_THREADS * GF_MAXC * 8, "gemv_fp8_mfma_fused: K=%d exceeds the %d values the prologue keeps in registers", K, GF_THREADS * GF_MAXC * 8);
+  LHRS_REQUIRE(K <= QX_MAX_K, "gemv_fp8_mfma_fused: K=%d exceeds the %d values the prologue keeps in registers", K, QX_MAX_K);
   const size_t sm = (size_t)B * K;
-  const dim3 grid(cdiv(N, 16)), blk(GF_THREADS);
+  const dim3 grid(cdiv(N, 16)), blk(QX_THREADS);
   hipStream_t s = (hipStream_t)stream;
 #define GOF(P, PK)                                                                                                                    \
   do {                                                                                                                                \

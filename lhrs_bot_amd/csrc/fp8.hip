@@ -8,14 +8,6 @@
 
 namespace {
 
-__device__ __forceinline__ int2 cvt8_e4m3(const float (&v)[8], float inv) {
-  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, 0, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, lo, true);
-  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, 0, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, hi, true);
-  return make_int2(lo, hi);
-}
-
 constexpr int FCH = 6;  // chunks of 8 columns per thread kept in registers: F <= 6 * 256 * 8 = 12288
 
 // act = silu(g) * u (rounded to bf16 like the unfused kernel), act8 = e4m3(act / scale), scale = max|act| / 448

@@ -12,12 +12,13 @@
 //   gemv4_kernel       batch 1, and batches 2..8 where K % 128 != 0: one wave per RPW rows, fp32 FMAs, the structure of gemv_kernel.
 //   gemv4_mfma_kernel  batch 2..16, K % 128 == 0: v_mfma_f32_16x16x32_bf16 with the batch as N, the structure of gemv_mfma_kernel; the A
 //                      fragments are dequantised in registers.
+//   Both take the activation prologue (stage_x) and the write-out (store_y, mfma_tile_store) of the bf16 GEMVs from decode_linear.h.
 //   level lookup  a 16-entry fp32 table in LDS: 16 words on 16 banks and equal addresses broadcast, so the divergent lookup is conflict-free
 //                 (a divergently indexed __constant__ array would serialise).
 // Cost per weight element: ~5.5 VALU instructions in the VALU kernel (shift and mask for the table offset, multiply, half a packed convert,
 // unpack, FMA) and ~3.5 in the MFMA kernel, plus one LDS lookup in both.  Both reach 1.1-1.55 TB/s of codes (measured per launch: DESIGN.md
 // "Decode from the 4-bit base"): not HBM-bound; which part of the dequantisation limits them has not been separated by counters.
-#include "common.h"
+#include "decode_linear.h"
 
 namespace {
 
@@ -34,42 +35,6 @@ __constant__ float LEVEL4[2][16] = {
 __device__ __forceinline__ void dequant8(uint32_t v, float a, const float* tab, uint32_t (&p)[4]) {
 #pragma unroll
   for (int t = 0; t < 4; ++t) p[t] = pack2bf(tab[(v >> (8 * t + 4)) & 15u] * a, tab[(v >> (8 * t)) & 15u] * a);
-}
-
-// the activation prologue of gemv_kernel / gemv_mfma_kernel for a block of T threads: rows b of x -> xs [NB][K] bf16 in LDS
-//   PRO 0 copy   1 HF RMSNorm bf16(w * bf16(x * rstd))   2 SwiGLU bf16(silu(x[k]) * x[K + k]) over x = [NB, 2K]
-template <int PRO, int T>
-__device__ __forceinline__ void stage_x(const bf16_t* __restrict__ x, long ldx, const bf16_t* __restrict__ norm_w, float eps, bf16_t* xs, float* red,
-                                        int NB, int K) {
-  const int tid = threadIdx.x, nx = K / 8;
-  for (int b = 0; b < NB; ++b) {
-    if (PRO == 2) {
-      for (int c = tid; c < nx; c += T) {
-        const uint4 g = *reinterpret_cast<const uint4*>(x + b * ldx + c * 8);
-        const uint4 u = *reinterpret_cast<const uint4*>(x + b * ldx + K + c * 8);
-        uint4 o;
-        o.x = pack2bf(silu(bflo(g.x)) * bflo(u.x), silu(bfhi(g.x)) * bfhi(u.x));
-        o.y = pack2bf(silu(bflo(g.y)) * bflo(u.y), silu(bfhi(g.y)) * bfhi(u.y));
-        o.z = pack2bf(silu(bflo(g.z)) * bflo(u.z), silu(bfhi(g.z)) * bfhi(u.z));
-        o.w = pack2bf(silu(bflo(g.w)) * bflo(u.w), silu(bfhi(g.w)) * bfhi(u.w));
-        *reinterpret_cast<uint4*>(xs + b * K + c * 8) = o;
-      }
-    } else {
-      float q = 0.f;
-      for (int c = tid; c < nx; c += T) {
-        const uint4 v = *reinterpret_cast<const uint4*>(x + b * ldx + c * 8);
-        *reinterpret_cast<uint4*>(xs + b * K + c * 8) = v;
-        if (PRO == 1)
-          q += bflo(v.x) * bflo(v.x) + bfhi(v.x) * bfhi(v.x) + bflo(v.y) * bflo(v.y) + bfhi(v.y) * bfhi(v.y) + bflo(v.z) * bflo(v.z) +
-               bfhi(v.z) * bfhi(v.z) + bflo(v.w) * bflo(v.w) + bfhi(v.w) * bfhi(v.w);
-      }
-      if (PRO == 1) {
-        const float rstd = rsqrtf(block_sum<T / 64>(q, red) / (float)K + eps);
-        __syncthreads();
-        for (int c = tid; c < K; c += T) xs[b * K + c] = f2bf(bf2f(norm_w[c]) * bf2f(f2bf(bf2f(xs[b * K + c]) * rstd)));
-      }
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -161,12 +126,7 @@ __global__ __launch_bounds__(256) void gemv4_kernel(const uint8_t* __restrict__ 
     for (int b = 0; b < NB; ++b) {
       const float s = wave_sum(acc[r][b]);
       const int row = row0 + r;
-      if (lane == 0 && row < N) {
-        float v = s;
-        if (res) v += bf2f(res[b * ldr + row]);
-        if (out_f32) reinterpret_cast<float*>(y)[b * ldy + row] = v;
-        else reinterpret_cast<bf16_t*>(y)[b * ldy + row] = f2bf(v);
-      }
+      if (lane == 0 && row < N) store_y(y, out_f32, b, ldy, row, s, res, ldr);
     }
 }
 
@@ -244,20 +204,7 @@ __global__ __launch_bounds__(512) void gemv4_mfma_kernel(const uint8_t* __restri
       areg[u] = anext[u];
     }
   }
-  // acc[r] = partial y[batch = fr][row0 + 4 * fg + r] of this wave's steps
-#pragma unroll
-  for (int r = 0; r < 4; ++r) part[wave][fg * 4 + r][fr] = acc[r];
-  __syncthreads();
-  const int i = tid >> 4, b = tid & 15;  // the first 256 threads = 16 rows x 16 batch columns
-  const int row = row0 + i;
-  if (tid < 256 && b < NB && row < N) {
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) v += part[w][i][b];
-    if (res) v += bf2f(res[b * ldr + row]);
-    if (out_f32) reinterpret_cast<float*>(y)[b * ldy + row] = v;
-    else reinterpret_cast<bf16_t*>(y)[b * ldy + row] = f2bf(v);
-  }
+  mfma_tile_store<8, 0>(part, acc, wave, fr, fg, row0, NB, N, nullptr, nullptr, res, ldr, y, ldy, out_f32);
 }
 
 constexpr long MFMA_STATIC_LDS = (8 + 8 * 16 * 17 + 16) * 4;  // red + part + tab of gemv4_mfma_kernel
@@ -313,12 +260,9 @@ extern "C" int lhrs_gemv4(const void* codes, long ldc, const float* absmax, long
   LHRS_REQUIRE(ldc % 16 == 0 && ldc >= K / 2 && (uintptr_t)codes % 16 == 0 && lda >= K / 64 && ldx % 8 == 0 && (uintptr_t)x % 16 == 0,
                "gemv4: strides / alignment (16-B lane loads): ldc=%ld lda=%ld ldx=%ld", ldc, lda, ldx);
   LHRS_REQUIRE(prologue >= 0 && prologue <= 2 && (prologue != 1 || norm_w != nullptr), "gemv4: prologue %d", prologue);
-  // the LDS rule of lhrs_gemv: at most 152 KiB of staged activations, and with the static LDS of the kernel a chunk goes to no more than
-  // the 160 KiB of a CU; a chunk of one row goes to the VALU kernel
+  // batches past the LDS are split as lhrs_gemv splits them; a chunk of one row goes to the VALU kernel
   const bool mfma = B >= 2 && K % 128 == 0;
-  const long lds_static = mfma ? MFMA_STATIC_LDS : VALU_STATIC_LDS;
-  const long lds_x = 152L * 1024 < 160L * 1024 - lds_static ? 152L * 1024 : 160L * 1024 - lds_static;
-  int bmax = (int)(lds_x / ((long)K * 2));
+  int bmax = staged_rows_max(K, mfma ? MFMA_STATIC_LDS : VALU_STATIC_LDS);
   if (mfma && prologue == 0) bmax = 16;  // the MFMA kernel reads x from L2
   LHRS_REQUIRE(bmax >= 1, "gemv4: one activation vector does not fit LDS (K=%d)", K);
   const long esz = out_f32 ? 4 : 2;

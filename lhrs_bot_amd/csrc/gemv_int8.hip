@@ -1,14 +1,14 @@
 // Decode from the LLM.int8 base (generate(weights="int8")): the single-token linears read the int8 rows and their row factors directly -
 // 1 B per weight per token, the e4m3 stream's size, with the base's exact codes - in the arithmetic of bitsandbytes' MatMul8bitLt that
 // int8.hip / gemm_fp8_256_kernel<true> reproduce for the multi-row products.
-//   int8_decode_prepare : ONE launch for the activation side of a decode linear (1..16 rows): prologue (copy / RMSNorm / SwiGLU, rounded
-//                         to bf16 where gemv_kernel's staging rounds), outlier columns (any row with |h| >= thr), per-row absmax of the
+//   int8_decode_prepare : ONE launch for the activation side of a decode linear (1..16 rows): prologue (copy / RMSNorm / SwiGLU, with the
+//                         roundings every decode linear shares: swiglu8 / rms_hf of decode_linear.h), outlier columns (any row with |h| >= thr), per-row absmax of the
 //                         entries below thr, int8 codes with the outlier columns zeroed, the ascending column list and the gathered 16-bit
 //                         activations.  The values of lhrs_int8_prepare(h) with M = B, bit for bit; nothing returns to the host.
 //   repack_int8_mfma    : int8 [N, ldw] rows -> the operand order the GEMV streams
 //   gemv_int8_kernel    : y[b][n] = f32(sum_k xq[b][k] WQ[n][k]) * fl(sx[b] * wscale[n])
 //                                   + sum_{j < meta[0]} xo[b][j] * bf16(WQ[n][idx[j]] * wscale[n])   (+ residual), one rounding at the store
-#include "common.h"
+#include "decode_linear.h"
 
 namespace {
 
@@ -25,19 +25,13 @@ __device__ __forceinline__ int dpack4(int a, int b, int c, int d) { return (a & 
 template <int PRO>
 __device__ __forceinline__ void dp_chunk(const bf16_t* __restrict__ xrow, const bf16_t* __restrict__ norm_w, float rstd, int K, int c, float (&h)[8]) {
   uint4 t = *reinterpret_cast<const uint4*>(xrow + c * 8);
-  if (PRO == 2) {
-    const uint4 u = *reinterpret_cast<const uint4*>(xrow + K + c * 8);
-    t.x = pack2bf(silu(bflo(t.x)) * bflo(u.x), silu(bfhi(t.x)) * bfhi(u.x));
-    t.y = pack2bf(silu(bflo(t.y)) * bflo(u.y), silu(bfhi(t.y)) * bfhi(u.y));
-    t.z = pack2bf(silu(bflo(t.z)) * bflo(u.z), silu(bfhi(t.z)) * bfhi(u.z));
-    t.w = pack2bf(silu(bflo(t.w)) * bflo(u.w), silu(bfhi(t.w)) * bfhi(u.w));
-  }
+  if (PRO == 2) t = swiglu8(t, *reinterpret_cast<const uint4*>(xrow + K + c * 8));
   unpack8(t, h);
   if (PRO == 1) {
     float g[8];
     unpack8(*reinterpret_cast<const uint4*>(norm_w + c * 8), g);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) h[e] = bf2f(f2bf(g[e] * bf2f(f2bf(h[e] * rstd))));  // HF LlamaRMSNorm roundings
+    for (int e = 0; e < 8; ++e) h[e] = rms_hf(h[e], g[e], rstd);
   }
 }
 
@@ -95,8 +89,7 @@ __global__ __launch_bounds__(DP_THREADS) void int8_decode_prepare_kernel(const b
         if (c < nch) {
           float v[8];
           unpack8(*reinterpret_cast<const uint4*>(xrow + c * 8), v);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) q += v[e] * v[e];
+          q = sumsq8_serial(q, v);
         }
       }
       rstd = rsqrtf(block_sum<DP_WAVES>(q, red) / (float)K + eps);
@@ -271,13 +264,9 @@ __global__ __launch_bounds__(GI_THREADS) void gemv_int8_kernel(const int8_t* __r
     for (int w = 0; w < GI_WAVES; ++w) sum += part[w][i][b];
     float v = __fmul_rn((float)sum, __fmul_rn(sx[b], wscale[row]));
     if (n > 0) v = __fadd_rn(v, opart[i][b]);
-    if (res) v = __fadd_rn(v, bf2f(res[(long)b * ldr + row]));
-    if (out_f32) reinterpret_cast<float*>(y)[(long)b * ldy + row] = v;
-    else reinterpret_cast<bf16_t*>(y)[(long)b * ldy + row] = f2bf(v);
+    store_y(y, out_f32, b, ldy, row, v, res, ldr);
   }
 }
-
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 

@@ -6,12 +6,11 @@
 //   dequant_mx4_rows : the inverse, exact in bf16 (level * 2^(byte - 127))
 //   repack_mx4_mfma  : row-major codes / scales -> the operand order gemv_mx4_kernel streams
 //   gemv_mx4_kernel  : y[b][n] = xscale[b] * sum_k x8[b][k] * w[n][k] (+ residual), 1..16 sequences
-#include "common.h"
+#include "decode_linear.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
-constexpr int GX_WAVES = 8, GX_THREADS = GX_WAVES * 64, GX_MAXC = 3;  // fused prologue: K <= GX_THREADS * GX_MAXC * 8 = 12288
 
 // ---- storage format ----------------------------------------------------------------------------------------------
 // one thread per block of 32: 64 B of bf16 in, 16 B of codes + 1 scale byte out
@@ -129,22 +128,23 @@ __global__ __launch_bounds__(256) void repack_mx4_mfma_kernel(const uint8_t* __r
 // differently by the hardware - registers 0-3 of lane (c, g) are k = 16 g .. +16 and registers 4-7 are k = 64 + 16 g .. +16 of the step, found
 // with one-hot operands through lhrs_gemv_mx4 and pinned by tests/test_mx4_gpu.py - so a lane reads bytes [16 g, +16) and [64 + 16 g, +16) of
 // its activation row, as gemv_fp8_mfma_kernel does (there on both operands, where any common order would do).
-// part[wave][16][17] is folded in wave order: no atomics, bit-reproducible.
+// The partial tiles of the waves are folded by mfma_tile_store of decode_linear.h.
 // PRO < 0: x8 / xscale come from global memory (any batch <= 16).  PRO 0 / 1 / 2 (batch <= 2): bf16 x; copy / RMSNorm (HF roundings) /
-// SwiGLU over [B, 2K] and the per-row e4m3 quantisation run in the block, bit for bit what the fused e4m3 GEMV of decode.hip computes.
+// SwiGLU over [B, 2K] and the per-row e4m3 quantisation run in the block, in the steps of stage_x_e4m3 of decode_linear.h (what the fused
+// e4m3 GEMV of decode.hip runs; this kernel has its block of QX_WAVES waves) and from the same pieces.
 template <int PRO>
-__global__ __launch_bounds__(GX_THREADS) void gemv_mx4_kernel(const uint8_t* __restrict__ Wc, const uint32_t* __restrict__ Ws,
+__global__ __launch_bounds__(QX_THREADS) void gemv_mx4_kernel(const uint8_t* __restrict__ Wc, const uint32_t* __restrict__ Ws,
                                                               const void* __restrict__ xin, long ldx, const float* __restrict__ xscale,
                                                               const bf16_t* __restrict__ norm_w, float eps, const bf16_t* res, long ldr, void* y,
                                                               long ldy, int NB, int N, int K, int out_f32) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // PRO >= 0: [NB][K] e4m3 bytes
-  __shared__ float part[GX_WAVES][16][17];
-  __shared__ float red[GX_WAVES];
+  __shared__ float part[QX_WAVES][16][17];
+  __shared__ float red[QX_WAVES];
   __shared__ float s_scale[2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
   const int row0 = blockIdx.x * 16;
   const int nsteps = K / 128, nd = (nsteps + 3) / 4;
-  const int per = ((nsteps + GX_WAVES - 1) / GX_WAVES + 3) / 4 * 4;  // K 11008: 86 steps = 7 x 12 + 2
+  const int per = ((nsteps + QX_WAVES - 1) / QX_WAVES + 3) / 4 * 4;  // K 11008: 86 steps = 7 x 12 + 2
   const int s_begin = min(wave * per, nsteps), s_end = min(nsteps, s_begin + per);
   const uint8_t* wp = Wc + (long)blockIdx.x * nsteps * 1024 + lane * 16;
   const uint32_t* sp = Ws + (long)blockIdx.x * nd * 64 + lane;
@@ -157,28 +157,23 @@ __global__ __launch_bounds__(GX_THREADS) void gemv_mx4_kernel(const uint8_t* __r
   const uint8_t* xp;
   if (PRO >= 0) {
     uint8_t* x8s = reinterpret_cast<uint8_t*>(smem);
+    // stage_x_e4m3 of decode_linear.h, step for step, on this kernel's own text: inlined from the header, the same arithmetic is allocated
+    // 2 VGPRs more (PRO 0) / fewer (PRO 1) and 2 SGPRs more (PRO 2) here, and this kernel's register table is kept as it was
     const bf16_t* x = reinterpret_cast<const bf16_t*>(xin);
     const int nch = K / 8;
     for (int b = 0; b < NB; ++b) {
-      float v[GX_MAXC][8], g[GX_MAXC][8];
+      float v[QX_MAXC][8], g[QX_MAXC][8];
       float q = 0.f;
 #pragma unroll
-      for (int i = 0; i < GX_MAXC; ++i) {
-        const int c = tid + i * GX_THREADS;
+      for (int i = 0; i < QX_MAXC; ++i) {
+        const int c = tid + i * QX_THREADS;
         if (c < nch) {
           uint4 t = *reinterpret_cast<const uint4*>(x + b * ldx + c * 8);
-          if (PRO == 2) {
-            const uint4 u = *reinterpret_cast<const uint4*>(x + b * ldx + K + c * 8);
-            t.x = pack2bf(silu(bflo(t.x)) * bflo(u.x), silu(bfhi(t.x)) * bfhi(u.x));
-            t.y = pack2bf(silu(bflo(t.y)) * bflo(u.y), silu(bfhi(t.y)) * bfhi(u.y));
-            t.z = pack2bf(silu(bflo(t.z)) * bflo(u.z), silu(bfhi(t.z)) * bfhi(u.z));
-            t.w = pack2bf(silu(bflo(t.w)) * bflo(u.w), silu(bfhi(t.w)) * bfhi(u.w));
-          }
+          if (PRO == 2) t = swiglu8(t, *reinterpret_cast<const uint4*>(x + b * ldx + K + c * 8));
           unpack8(t, v[i]);
           if (PRO == 1) {
             unpack8(*reinterpret_cast<const uint4*>(norm_w + c * 8), g[i]);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) q += v[i][e] * v[i][e];
+            q = sumsq8_serial(q, v[i]);
           }
         } else {
 #pragma unroll
@@ -186,33 +181,27 @@ __global__ __launch_bounds__(GX_THREADS) void gemv_mx4_kernel(const uint8_t* __r
         }
       }
       if (PRO == 1) {
-        const float rstd = rsqrtf(block_sum<GX_WAVES>(q, red) / (float)K + eps);
+        const float rstd = rsqrtf(block_sum<QX_WAVES>(q, red) / (float)K + eps);
 #pragma unroll
-        for (int i = 0; i < GX_MAXC; ++i)
-          if (tid + i * GX_THREADS < nch) {
+        for (int i = 0; i < QX_MAXC; ++i)
+          if (tid + i * QX_THREADS < nch) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[i][e] = bf2f(f2bf(g[i][e] * bf2f(f2bf(v[i][e] * rstd))));  // HF LlamaRMSNorm roundings
+            for (int e = 0; e < 8; ++e) v[i][e] = rms_hf(v[i][e], g[i][e], rstd);
           }
       }
       float m = 0.f;
 #pragma unroll
-      for (int i = 0; i < GX_MAXC; ++i)
+      for (int i = 0; i < QX_MAXC; ++i)
 #pragma unroll
         for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(v[i][e]));
-      m = block_max<GX_WAVES>(m, red);
+      m = block_max<QX_WAVES>(m, red);
       const float sc = m > 0.f ? m / 448.f : 1.f;
       if (tid == 0) s_scale[b] = sc;
       const float inv = 1.f / sc;
 #pragma unroll
-      for (int i = 0; i < GX_MAXC; ++i) {
-        const int c = tid + i * GX_THREADS;
-        if (c < nch) {
-          int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][0] * inv, v[i][1] * inv, 0, false);
-          lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][2] * inv, v[i][3] * inv, lo, true);
-          int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][4] * inv, v[i][5] * inv, 0, false);
-          hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][6] * inv, v[i][7] * inv, hi, true);
-          *reinterpret_cast<int2*>(x8s + (size_t)b * K + c * 8) = make_int2(lo, hi);
-        }
+      for (int i = 0; i < QX_MAXC; ++i) {
+        const int c = tid + i * QX_THREADS;
+        if (c < nch) *reinterpret_cast<int2*>(x8s + (size_t)b * K + c * 8) = cvt8_e4m3(v[i], inv);
       }
     }
     __syncthreads();
@@ -252,25 +241,8 @@ __global__ __launch_bounds__(GX_THREADS) void gemv_mx4_kernel(const uint8_t* __r
       wsc = wscn;
     }
   }
-  // acc[r] = partial y[batch = fr][row0 + 4 fg + r] of this wave's steps
-#pragma unroll
-  for (int r = 0; r < 4; ++r) part[wave][fg * 4 + r][fr] = acc[r];
-  __syncthreads();
-  const int i = tid >> 4, b = tid & 15;
-  const int row = row0 + i;
-  if (tid < 256 && b < NB && row < N) {
-    const float xs_b = PRO >= 0 ? s_scale[b] : xscale[b];
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < GX_WAVES; ++w) v += part[w][i][b];
-    v *= xs_b;
-    if (res) v += bf2f(res[b * ldr + row]);
-    if (out_f32) reinterpret_cast<float*>(y)[b * ldy + row] = v;
-    else reinterpret_cast<bf16_t*>(y)[b * ldy + row] = f2bf(v);
-  }
+  mfma_tile_store<QX_WAVES, 1>(part, acc, wave, fr, fg, row0, NB, N, nullptr, PRO >= 0 ? s_scale : xscale, res, ldr, y, ldy, out_f32);
 }
-
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -316,7 +288,7 @@ extern "C" int lhrs_gemv_mx4(const void* codes_t, const void* scales_t, const vo
   LHRS_REQUIRE(B >= 1 && B <= 16 && N > 0 && K >= 128 && K % 128 == 0, "gemv_mx4: B=%d (1..16) N=%d K=%d (K %% 128 == 0)", B, N, K);
   LHRS_REQUIRE(codes_t && scales_t && x8 && xscale && y && al16(codes_t) && al16(scales_t) && al16(x8) && ldx % 16 == 0 && ldx >= K,
                "gemv_mx4: pointers / strides (ldx=%ld)", ldx);
-  hipLaunchKernelGGL((gemv_mx4_kernel<-1>), dim3(cdiv(N, 16)), dim3(GX_THREADS), 0, (hipStream_t)stream, (const uint8_t*)codes_t,
+  hipLaunchKernelGGL((gemv_mx4_kernel<-1>), dim3(cdiv(N, 16)), dim3(QX_THREADS), 0, (hipStream_t)stream, (const uint8_t*)codes_t,
                      (const uint32_t*)scales_t, x8, ldx, xscale, (const bf16_t*)nullptr, 0.f, (const bf16_t*)residual, ldr, y, ldy, B, N, K,
                      out_f32);
   LHRS_CHECK_LAUNCH("gemv_mx4");
@@ -332,9 +304,9 @@ extern "C" int lhrs_gemv_mx4_fused(const void* codes_t, const void* scales_t, co
   LHRS_REQUIRE(codes_t && scales_t && x && y && al16(codes_t) && al16(scales_t) && al16(x) && ldx % 8 == 0 && prologue >= 0 && prologue <= 2 &&
                    (prologue != 1 || (norm_w && al16(norm_w))) && ldx >= (prologue == 2 ? 2L * K : (long)K),
                "gemv_mx4_fused: args (ldx=%ld prologue=%d)", ldx, prologue);
-  LHRS_REQUIRE(K <= GX_THREADS * GX_MAXC * 8, "gemv_mx4_fused: K=%d exceeds the %d values the prologue keeps in registers", K, GX_THREADS * GX_MAXC * 8);
+  LHRS_REQUIRE(K <= QX_MAX_K, "gemv_mx4_fused: K=%d exceeds the %d values the prologue keeps in registers", K, QX_MAX_K);
   const size_t sm = (size_t)B * K;
-  const dim3 grid(cdiv(N, 16)), blk(GX_THREADS);
+  const dim3 grid(cdiv(N, 16)), blk(QX_THREADS);
 #define GOX(P)                                                                                                                      \
   hipLaunchKernelGGL((gemv_mx4_kernel<P>), grid, blk, sm, (hipStream_t)stream, (const uint8_t*)codes_t, (const uint32_t*)scales_t, x, ldx, \
                      (const float*)nullptr, (const bf16_t*)norm_w, eps, (const bf16_t*)residual, ldr, y, ldy, B, N, K, out_f32)

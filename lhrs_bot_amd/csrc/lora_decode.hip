@@ -12,10 +12,10 @@
 //
 // lora_down streams 0.5-3 MB of stacked A rows: 8 rows per workgroup would put a [24, 4096] A on 3 CUs, so K is cut into up to 16 slices of
 // whole 64-element chunks (grid = R / 8 x slices) and the slice sums meet in lora_up, in ascending slice order.  The activation prologues are
-// those of gemv_kernel, rounded where it rounds (RMSNorm: bf16(w * bf16(x * rstd)) with rstd from the whole row, which every workgroup
-// forms itself from L2; SwiGLU: bf16(silu(g) * u)), so the adapter sees the activation the base product sees.
+// those of gemv_kernel, built from the same pieces of decode_linear.h (RMSNorm: bf16(w * bf16(x * rstd)) with rstd from the whole row, which
+// every workgroup forms itself from L2; SwiGLU: bf16(silu(g) * u)), so the adapter sees the activation the base product sees.
 // lora_up reads of Bfull [N, ldb] only the one non-zero block of each block-diagonal row: columns [(n / fout) r, +r).
-#include "common.h"
+#include "decode_linear.h"
 
 namespace {
 
@@ -46,11 +46,7 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const bf16_t* __restrict
     rstd[b] = 1.f;
     if (pro == 1 && b < B) {  // the whole row, as the GEMV blocks do: thread t takes the 16-B chunks t, t + 256, ...
       float q = 0.f;
-      for (int c = tid; c < K / 8; c += 256) {
-        const uint4 v = *reinterpret_cast<const uint4*>(x + b * ldx + c * 8);
-        q += bflo(v.x) * bflo(v.x) + bfhi(v.x) * bfhi(v.x) + bflo(v.y) * bflo(v.y) + bfhi(v.y) * bfhi(v.y) + bflo(v.z) * bflo(v.z) +
-             bfhi(v.z) * bfhi(v.z) + bflo(v.w) * bflo(v.w) + bfhi(v.w) * bfhi(v.w);
-      }
+      for (int c = tid; c < K / 8; c += 256) q += sumsq8_chunk(*reinterpret_cast<const uint4*>(x + b * ldx + c * 8));
       rstd[b] = rsqrtf(block_sum<4>(q, red) / (float)K + eps);
     }
   }
@@ -61,18 +57,14 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const bf16_t* __restrict
         const bf16_t* xp = x + b * ldx + k0 + c * 8;
         uint4 o = *reinterpret_cast<const uint4*>(xp);
         if (pro == 2) {
-          const uint4 u = *reinterpret_cast<const uint4*>(xp + K);
-          o.x = pack2bf(silu(bflo(o.x)) * bflo(u.x), silu(bfhi(o.x)) * bfhi(u.x));
-          o.y = pack2bf(silu(bflo(o.y)) * bflo(u.y), silu(bfhi(o.y)) * bfhi(u.y));
-          o.z = pack2bf(silu(bflo(o.z)) * bflo(u.z), silu(bfhi(o.z)) * bfhi(u.z));
-          o.w = pack2bf(silu(bflo(o.w)) * bflo(u.w), silu(bfhi(o.w)) * bfhi(u.w));
+          o = swiglu8(o, *reinterpret_cast<const uint4*>(xp + K));
         } else if (pro == 1) {
           float v[8], w[8];
           unpack8(o, v);
           unpack8(*reinterpret_cast<const uint4*>(norm_w + k0 + c * 8), w);
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = w[e] * bf2f(f2bf(v[e] * rstd[b]));
-          o = pack8(v);
+          o = pack8(v);  // rms_hf: its last rounding is the one pack8 does (through the helper the compiler converts twice)
         }
         *reinterpret_cast<uint4*>(xs + b * ks + c * 8) = o;
       }

@@ -170,13 +170,7 @@ __device__ __forceinline__ void store_row_e4m3(unsigned char* y8, float* scale_o
   if (lane == 0) *scale_out = sc;
   const float inv = 1.f / sc;
 #pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[c][0] * inv, v[c][1] * inv, 0, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[c][2] * inv, v[c][3] * inv, lo, true);
-    int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[c][4] * inv, v[c][5] * inv, 0, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[c][6] * inv, v[c][7] * inv, hi, true);
-    *reinterpret_cast<int2*>(y8 + (c * 64 + lane) * 8) = make_int2(lo, hi);
-  }
+  for (int c = 0; c < NCH; ++c) *reinterpret_cast<int2*>(y8 + (c * 64 + lane) * 8) = cvt8_e4m3(v[c], inv);
 }
 
 // ---------------------------------------------------------------- RMSNorm

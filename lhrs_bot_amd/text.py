@@ -1005,32 +1005,30 @@ class TextModal:
                 return s.actb, hk.PRO_NONE, norm_w
             return x_in, pro, norm_w
 
+        def quantised(x_in, K, pro, norm_w):
+            """batch > 2 on e4m3 activations: the quantising producer of the prologue -> (e4m3 rows, per-row scales) in s.x8 / s.a8"""
+            if pro == hk.PRO_RMSNORM:
+                return hk.rmsnorm_fwd_q(x_in, norm_w, self.eps, want_bf16=False, q_out=s.x8)[1]
+            if pro == hk.PRO_SWIGLU:
+                return hk.swiglu_fwd_q(x_in, ff, q_out=s.a8)[1:]
+            # K = ff: the materialised SwiGLU of the batched live-adapter path (MXFP4).  `batched` excludes fp8, so a prologue-free fp8
+            # linear always has K = d and lands in s.x8
+            return hk.quant_fp8_rows(x_in, out=s.x8 if K == d else s.a8)
+
         def base(w, sc, x_in, out, K, pro=hk.PRO_NONE, norm_w=None, residual=None, out_f32=False):
-            if fp8 and B <= 2:  # prologue + activation quantisation inside the GEMV: five launches per layer
-                hk.gemv_fp8_mfma_fused(w, sc, x_in, out, K, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
-                return
-            if fp8:
-                if pro == hk.PRO_RMSNORM:
-                    _, q = hk.rmsnorm_fwd_q(x_in, norm_w, self.eps, want_bf16=False, q_out=s.x8)
-                elif pro == hk.PRO_SWIGLU:
-                    _, a8, sa = hk.swiglu_fwd_q(x_in, ff, q_out=s.a8)
-                    q = (a8, sa)
+            if fp8:  # up to batch 2 prologue + activation quantisation run inside the GEMV: five launches per layer
+                if B <= 2:
+                    hk.gemv_fp8_mfma_fused(w, sc, x_in, out, K, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
                 else:
-                    q = hk.quant_fp8_rows(x_in, out=s.x8)
-                hk.gemv_fp8_mfma(w, sc, q[0], q[1], out, residual=residual, out_f32=out_f32)
+                    x8, sx = quantised(x_in, K, pro, norm_w)
+                    hk.gemv_fp8_mfma(w, sc, x8, sx, out, residual=residual, out_f32=out_f32)
                 return
-            if isinstance(w, hk.PackedMX4):   # as the fp8 branch: fused up to batch 2, else the quantising producers + the x8 form
+            if isinstance(w, hk.PackedMX4):   # as the fp8 branch
                 if B <= 2:
                     hk.gemv_mx4_fused(w, x_in, out, K, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
-                    return
-                if pro == hk.PRO_RMSNORM:
-                    _, q = hk.rmsnorm_fwd_q(x_in, norm_w, self.eps, want_bf16=False, q_out=s.x8)
-                elif pro == hk.PRO_SWIGLU:
-                    _, a8, sa = hk.swiglu_fwd_q(x_in, ff, q_out=s.a8)
-                    q = (a8, sa)
                 else:
-                    q = hk.quant_fp8_rows(x_in, out=s.x8 if K == d else s.a8)   # K = ff: the materialised SwiGLU of the batched live-adapter path
-                hk.gemv_mx4(w, q[0], q[1], out, residual=residual, out_f32=out_f32)
+                    x8, sx = quantised(x_in, K, pro, norm_w)
+                    hk.gemv_mx4(w, x8, sx, out, residual=residual, out_f32=out_f32)
                 return
             if isinstance(w, hk.PackedI8):   # prologue, outlier split and quantisation in one launch, then the int8 weight stream
                 hk.int8_decode_prepare(x_in, K, s.i8ws, prologue=pro, norm_w=norm_w, eps=self.eps)
