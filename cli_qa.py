@@ -5,7 +5,7 @@ flag-compatible (`-c Config/multi_modal_eval.yaml --model-path <FINAL.pt dir> --
     build_model -> custom_load_state_dict -> CLIP preprocess (HIP) -> llava_llama_2 prompt -> tokenizer_image_token ->
     KeywordsStoppingCriteria(["</s>"]) -> model.generate(do_sample=True, temperature=0.4, max_new_tokens=512, streamer=...)
 
-The prefill runs on the GEMM path, the per-token step is one captured hipGraph (lhrs_bot_amd/text.py `_decode_session`);
+The prefill runs on the GEMM path, the per-token step is one captured hipGraph (lhrs_bot_amd/generation.py `DecodeSession`);
 `bits: 8` in the YAML (or `--opts bits 8`) streams e4m3 weights through the MFMA GEMV; `--decode-weights 4bit` with `bits: 4` streams
 the NF4 / FP4 codes of the 4-bit base (lhrs_gemv4); `--decode-weights mxfp4` (any base) streams OCP MXFP4 copies on the FP4 MFMA
 (lhrs_gemv_mx4); `--decode-weights int8` with `bits: 8` streams the int8 rows of the LLM.int8 base (lhrs_gemv_int8).

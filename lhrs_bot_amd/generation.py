@@ -1,0 +1,567 @@
+"""Single-token decoding and generation for `TextModal` (text.py binds the functions below under their `TextModal` names): FORMATS, the one
+table of what `generate(weights=...)` can stream; DecodeSession, the static buffers and launch list of one single-token step; the token loops."""
+import dataclasses
+import math
+import os
+from typing import Callable, Optional
+
+import torch
+
+from . import kernels as hk
+
+WEIGHT_NAMES = ("qkv_w", "o_w", "gu_w", "down_w")   # the fused decoder linears of a layer dict
+
+
+# ------------------------------------------------------------------------------------------------- the weight formats
+@dataclasses.dataclass
+class WeightFormat:
+    """One entry of FORMATS: what `generate(weights=...)` streams through the decoder linears of the single-token step."""
+    operand: str                     # L[<weight name> + operand] is what the step streams ...
+    pack_weight: Callable            # ... made by pack_weight(L, <weight name>) for every layer, at the first session that needs it
+    acts: str                        # the activation side, and with it the linear (`linear`) and its static operand buffers (`buffers`)
+    kernels: tuple                   # names of the hk wrappers of that linear
+    scale: Optional[str] = None      # suffix of the per-row scales that go with the operand
+    check: Callable = lambda m, pack: None   # -> error text on a model it cannot serve; pack: asked by the public pack method, not by generate()
+    optional: bool = False           # the row-major weight streams as it is; the operand is made and read from batch 2 only ("bf16")
+    own_head: bool = False           # lm_head has this form too; otherwise the "bf16" entry serves it, whatever the decoder streams
+    stages: bool = True              # from batch 4 RMSNorm / SwiGLU may run once into s.hn / s.actb, not once per block of the weight stream
+    int8_gemm: bool = False          # prefill and the batch > 16 step run the LLM.int8 products: the whole call is in that arithmetic
+
+    def pack(self, m) -> None:
+        err = self.check(m, True)
+        if err:
+            raise ValueError(err)
+        if self.scale and "qkv_w" + self.scale not in m.p["layers"][0]:   # only "fp8" can lack them: int8's scales ARE its base (checked above)
+            quantize_fp8(m)
+        for L in m.p["layers"]:
+            for k in WEIGHT_NAMES:
+                L[k + self.operand] = self.pack_weight(L, k)
+        if self.own_head:
+            m.p["lm_head" + self.operand] = self.pack_weight(m.p, "lm_head")
+
+    def ensure(self, m, packed16) -> None:
+        """lazy packing, at the first session that needs it"""
+        if (packed16 or not self.optional) and "qkv_w" + self.operand not in m.p["layers"][0]:
+            self.pack(m)
+        if packed16 and "lm_headp" not in m.p:  # lm_head alone: pack_bf16_decode() would add 13.5 GB of re-tiled decoder weights that this mode never reads
+            m.p["lm_headp"] = hk.repack_bf16_mfma(m.p["lm_head"])
+
+    def weight(self, L, name, packed16):
+        """(weight, per-row scales or None) of L[name]; `L` may be the parameter dict itself and `name` "lm_head" """
+        return L[name + (self.operand if packed16 or not self.optional else "")], (L[name + self.scale] if self.scale else None)
+
+    def buffers(self, s) -> None:
+        dev, B = s.m.device, s.B
+        if self.acts == "e4m3":   # operands of the block-scaled MFMA: (codes, per-row scale) of both activation widths (graph capture: no allocation)
+            s.x8 = (torch.zeros((B, s.m.d), device=dev, dtype=torch.uint8), torch.zeros(B, device=dev, dtype=torch.float32))
+            s.a8 = (torch.zeros((B, s.m.ff), device=dev, dtype=torch.uint8), torch.zeros(B, device=dev, dtype=torch.float32))
+        elif self.acts == "int8":
+            s.i8ws = hk.Int8DecodeWorkspace(dev, B, max(s.m.d, s.m.ff), s.m._i8ws.threshold if s.m._i8ws is not None else 6.0)
+
+    def linear(self, s, w, sc, x, out, K, pro, norm_w, **o):
+        """out = pro(x) W^T (+ residual) on session `s`; o: residual, out_f32.  The "bf16" entry also runs as the HEAD format of the other formats'
+        sessions: what it reads from `s` (`batched` behind `staged`) is set by the session's own format, whose `stages` must suit both."""
+        k0, k1 = (getattr(hk, k) for k in self.kernels)
+        ws = (w,) if sc is None else (w, sc)
+        if self.acts == "int8":   # prologue, outlier split and quantisation in one launch, then the int8 weight stream
+            k0(x, K, s.i8ws, prologue=pro, norm_w=norm_w, eps=s.m.eps)
+            k1(w, sc, s.i8ws, out, K, **o)
+        elif self.acts == "bf16":  # prologue inside the GEMV, or materialised once (`staged`)
+            x, pro, norm_w = s.staged(x, pro, norm_w)
+            k0(w, x, out, K, prologue=pro, norm_w=norm_w, eps=s.m.eps, **o)
+        elif s.B <= 2:            # e4m3: prologue + activation quantisation inside the GEMV (five launches per layer) ...
+            k0(*ws, x, out, K, prologue=pro, norm_w=norm_w, eps=s.m.eps, **o)
+        else:                     # ... above batch 2 the quantising producer of the prologue, then the GEMV
+            k1(*ws, *s.quantised(x, K, pro, norm_w), out, **o)
+
+
+def quantize_fp8(m):
+    for L, k in [(L, k) for L in m.p["layers"] for k in WEIGHT_NAMES] + [(m.p, "lm_head")]:
+        L[k + "8"], L[k + "8s"] = hk.quant_fp8_rows(L[k])
+
+
+def _check_int8(m, pack):
+    if (pack and not m.p["layers"]) or "qkv_wi8" not in m.p["layers"][0]:
+        return NO_BASE["int8"][pack]
+    if not pack and (m.d % 64 or m.ff % 64 or max(m.d, m.ff) > 16384):
+        return f'weights="int8" needs hidden sizes that are multiples of 64 (the MFMA step) and at most 16384, got {m.d} and {m.ff}'
+
+
+def int8_gemm(weights) -> bool:   # False for a `weights` the table does not know: that is rejected where the session is built
+    return weights in FORMATS and FORMATS[weights].int8_gemm
+
+
+NO_BASE = {  # format -> (text of generate(weights=...), text of the public pack method) on a model without the base it streams
+    "4bit": ('weights="4bit" needs the 4-bit base: quantize_base(4, quant_type, double_quant) (YAML `bits: 4`)',
+             "pack4_decode: the decoder is not on the 4-bit base - call quantize_base(4, quant_type, double_quant) first"),
+    "int8": ('weights="int8" needs the LLM.int8 base: quantize_base(8, "int8") (YAML `bits: 8`)',
+             'pack_int8_decode: the decoder is not on the LLM.int8 base - call quantize_base(8, "int8") first')}
+FORMATS = {  # lm_head is quantised in no base of the reference: it streams bf16 in every format but "fp8"
+    "bf16": WeightFormat("p", lambda L, k: hk.repack_bf16_mfma(L[k]), "bf16", ("gemv_fused", "gemv_fused"), optional=True, own_head=True),
+    "fp8": WeightFormat("8p", lambda L, k: hk.repack_fp8_mfma(L[k + "8"]), "e4m3", ("gemv_fp8_mfma_fused", "gemv_fp8_mfma"), scale="8s", own_head=True, stages=False),
+    "4bit": WeightFormat("4p", lambda L, k: hk.pack4_decode(L[k + "q4"], *L[k].shape), "bf16", ("gemv4", "gemv4"),
+                         check=lambda m, pack: None if m.base4 else NO_BASE["4bit"][pack]),
+    "mxfp4": WeightFormat("mx4", lambda L, k: hk.repack_mx4_mfma(*hk.quant_mx4_rows(L[k])), "e4m3", ("gemv_mx4_fused", "gemv_mx4"), check=lambda m, pack: None
+                          if pack or not (m.d % 128 or m.ff % 128) else f'weights="mxfp4" needs hidden sizes that are multiples of 128 (the MFMA step), got {m.d} and {m.ff}'),
+    "int8": WeightFormat("i8p", lambda L, k: hk.repack_int8_mfma(L[k + "i8"]), "int8", ("int8_decode_prepare", "gemv_int8"), scale="i8s", check=_check_int8, int8_gemm=True),
+}
+DECODE_SUFFIXES = tuple(f.operand for f in FORMATS.values())   # the `<weight name><suffix>` keys the packers create (`quantize_fp8`: "8", "8s")
+
+
+def check_kv_cache(m, kv_cache, rows, num_beams=1):
+    """generate(kv_cache=...), "fp8" = the kv8 format of csrc/decode_kv8.hip: what it cannot serve raises here, before anything is allocated"""
+    if kv_cache not in ("bf16", "fp8"):
+        raise ValueError(f"kv_cache={kv_cache!r}: expected 'bf16' or 'fp8'")
+    if kv_cache == "bf16":
+        return
+    if m.hd != 128:
+        raise ValueError(f'kv_cache="fp8" needs head_dim 128 (one scale byte per 128-value head row), this model has head_dim {m.hd}')
+    if rows > 16:
+        raise ValueError(f'kv_cache="fp8" with batch (x num_beams) {rows} > 16: beyond 16 rows the single-token step attends through attn_fwd '
+                         'over bf16 caches, which the fp8 cache does not have')
+    if num_beams > 1 and m.heads % 16:
+        raise ValueError(f'kv_cache="fp8" with num_beams > 1 needs a head count that is a multiple of 16 (kv_beam_reorder moves the scale '
+                         f'bytes of a position in 16-byte chunks), this model has {m.heads} heads')
+
+
+def alloc_kv(m, rows, kv_cache):
+    """per layer: (K, V) bf16 [rows, d], or for kv_cache="fp8" (K codes, V codes uint8 [rows, d], K scales, V scales uint8 [rows, H])"""
+    def t(cols, dtype):
+        return torch.empty((rows, cols), device=m.device, dtype=dtype)
+    if kv_cache == "fp8":
+        return [(t(m.d, torch.uint8), t(m.d, torch.uint8), t(m.heads, torch.uint8), t(m.heads, torch.uint8)) for _ in m.p["layers"]]
+    return [(t(m.d, torch.bfloat16), t(m.d, torch.bfloat16)) for _ in m.p["layers"]]
+
+
+# ------------------------------------------------------------------------------------------------- the GEMM step (prefill, batch > 16)
+def layer_step(m, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None, int8=False):
+    """One decoder layer over S_new new positions per sequence behind `ctx` cached ones (prefill: ctx = 0).  li = the layer's index, under
+    adapters="live" or int8: the linears are the training forward's (`_lin` / `_gu_fwd`; dropout is off) - adapters on the bf16 base weights,
+    or with int8 (weights="int8" only) `hk.int8_linear` on the int8 rows with the adapters of a live store on top."""
+    d, H, hd, ff = m.d, m.heads, m.hd, m.ff
+    M = x.shape[0]
+    i8 = (lambda name: (L[name + "i8"], L[name + "i8s"])) if int8 else (lambda name: None)
+    h = hk.rmsnorm_fwd(x, L["ln1_w"], m.eps)
+    if li is None:
+        qkv = hk.gemm_rope_fwd(h, L["qkv_w"], m.cos, m.sin, pos_mod=S_new, pos0=ctx, rope_cols=2 * d, head_dim=hd)
+    else:
+        qkv = m._lin(li, "qkv", h, L["qkv_w"], rope=(S_new, ctx), i8=i8("qkv_w"))
+    o = torch.empty((M, d), device=m.device, dtype=torch.bfloat16)
+    if len(cache) == 4:
+        # kv_cache="fp8", prefill only: attention reads the exact bf16 K / V of the prompt straight out of `qkv` (desc: kv_off = b * S_new),
+        # so the prompt's logits are those of the bf16-cache mode bit for bit; the rows enter the cache as codes + scale bytes
+        assert ctx == 0, "the kv8 cache has no multi-row step after the prefill (generate() rejects batch > 16)"
+        kc8, vc8, ks, vs = cache
+        hk.attn_fwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True,
+                    1.0 / math.sqrt(hd), key_mask=kmask)
+        for b in range(B):
+            rows = qkv[b * S_new:(b + 1) * S_new]
+            hk.kv8_quant_rows(rows[:, d:2 * d], kc8, ks, b * max_ctx, H)
+            hk.kv8_quant_rows(rows[:, 2 * d:], vc8, vs, b * max_ctx, H)
+    else:
+        kc, vc = cache
+        row_b = d * 2
+        for b in range(B):  # append the new K / V rows of sequence b at position ctx of its cache
+            src = qkv.data_ptr() + b * S_new * 3 * row_b
+            hk.copy_2d(kc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + row_b, 3 * row_b, row_b, S_new)
+            hk.copy_2d(vc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + 2 * row_b, 3 * row_b, row_b, S_new)
+        hk.attn_fwd(qkv[:, :d], kc, vc, o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True, 1.0 / math.sqrt(hd), key_mask=kmask)
+    if li is not None:   # the fused gate|up + SwiGLU GEMM of the training forward; the arm below runs gemm_nt + swiglu_fwd (different kernels)
+        x = m._lin(li, "o", o, L["o_w"], residual=x, i8=i8("o_w"))
+        h = hk.rmsnorm_fwd(x, L["ln2_w"], m.eps, out=h)
+        _, act, _ = m._gu_fwd(li, h, L["gu_w"], None, i8=i8("gu_w"))
+        return m._lin(li, "down", act, L["down_w"], residual=x, i8=i8("down_w"))
+    x = hk.gemm_nt(o, L["o_w"], residual=x)
+    h = hk.rmsnorm_fwd(x, L["ln2_w"], m.eps, out=h)
+    act = hk.swiglu_fwd(hk.gemm_nt(h, L["gu_w"]), ff)
+    return hk.gemm_nt(act, L["down_w"], residual=x)
+
+
+def gemm_logits(m, x, B, S, ctx, caches, row_stride, kv8, kmask, lora, weights):
+    """S new positions per sequence (rows of x) behind `ctx` cached ones through the GEMM path -> fp32 logits [B, V] of the last one: the
+    prefill (ctx = 0) and the step of a batch > 16.  Sequence b owns the cache rows from b * row_stride (`num_beams * max_ctx` under beams).
+    kv8, prefill only: the attention reads K / V out of the qkv buffer itself, where sequence b starts at row b * S."""
+    i8 = int8_gemm(weights)
+    desc = hk.make_desc([(b * S, S, b * (S if kv8 else row_stride), ctx + S, ctx + S, ctx) for b in range(B)], m.device)
+    for li, (L, cache) in enumerate(zip(m.p["layers"], caches)):
+        x = m._layer_step(L, x, B, S, ctx, cache, desc, row_stride, kmask, li=li if lora is not None or i8 else None, int8=i8)
+    hn = hk.rmsnorm_fwd(x.view(B, S, -1)[:, -1].contiguous(), m.p["norm_w"], m.eps)
+    return hk.gemm_nt(hn, m.p["lm_head"], out_f32=True)
+
+
+def decode_context(m, mask, B, S0, max_new_tokens):
+    """-> (max_ctx checked against the RoPE table, key mask [B, max_ctx] of LEFT-padded prompts or None).  Batched evaluation (main_vqa.py:205-214):
+    HF keeps position_ids = arange and hides the keys whose (spliced) attention_mask is 0; every generated position is visible."""
+    max_ctx = S0 + max_new_tokens
+    if max_ctx > m.cos.shape[0]:
+        raise ValueError(f"prompt ({S0}) + max_new_tokens ({max_new_tokens}) exceeds the {m.cos.shape[0]} positions of the RoPE table")
+    kmask = None
+    if mask is not None and not bool(mask.bool().all()):
+        kmask = torch.ones((B, max_ctx), device=m.device, dtype=torch.uint8)
+        kmask[:, :S0] = mask.to(device=m.device, dtype=torch.uint8)
+    return max_ctx, kmask
+
+
+def step_or_replay(s, step, use_graph, n_done):
+    """One more token of session `s`: `step()` eagerly first (lazy kernel attributes), captured at the second token, a replay from then on"""
+    if use_graph and s.graph is None and n_done >= 2:
+        g = hk.HipGraph()
+        g.begin()
+        step()
+        g.end()
+        s.graph = g
+    if s.graph is not None:
+        s.graph.launch()
+    else:
+        step()
+
+
+# ------------------------------------------------------------------------------------------------- the single-token step
+class DecodeSession:
+    """Static buffers + one captured hipGraph for the single-token step (batch <= 16): embedding gather, 32 x [QKV GEMV with RMSNorm, RoPE +
+    KV append + attention over the cache, O GEMV + residual, gate|up GEMV with RMSNorm, down GEMV with SwiGLU + residual], lm_head GEMV with the
+    final norm -> fp32 logits.  Context length / positions live on the device (decode_advance): one capture serves every token.
+
+    lora = a LoraStore (adapters="live"): a linear of an adapted group becomes `hk.lora_down` on the activation the base product sees, the
+    format's GEMV into the fp32 `acc` without its residual, `hk.lora_up` into the output with the residual - y = bf16(x W^T + (s x A^T) B^T
+    + residual) on one fp32 value, as training's `_lin`.  The store's bf16 shadow and `Bfull` are read in place (`LoraStore.refresh` rewrites
+    their storage): no copy of an adapter is held.  kv_cache="fp8": `caches` holds (K codes, V codes, K scales, V scales) per layer."""
+
+    def __init__(self, m, B, max_ctx, caches, max_new, weights="bf16", kmask=None, lora=None, kv_cache="bf16"):
+        m._check_kv_cache(kv_cache, B)
+        if weights not in FORMATS:
+            raise ValueError(f"weights={weights!r}: expected 'bf16', 'fp8', '4bit', 'mxfp4' or 'int8'")
+        fmt = FORMATS[weights]
+        err = fmt.check(m, False)
+        if err:
+            raise ValueError(err)
+        dev, d, ff, bf = m.device, m.d, m.ff, torch.bfloat16
+        self.m, self.fmt, self.B, self.max_ctx, self.max_new, self.caches, self.kmask, self.lora = m, fmt, B, max_ctx, max_new, caches, kmask, lora
+        self.kv8, self.graph, self.head = kv_cache == "fp8", None, fmt if fmt.own_head else FORMATS["bf16"]
+        self.packed16 = self.head.optional and B >= 2 and d % 128 == 0 and ff % 128 == 0   # batched bf16: the MFMA GEMV on re-tiled weights
+        fmt.ensure(m, self.packed16)
+
+        def z(*shape, dtype=bf):
+            return torch.zeros(shape, device=dev, dtype=dtype)
+        self.x, self.x2, self.o, self.qkv, self.gu = z(B, d), z(B, d), z(B, d), z(B, 3 * d), z(B, 2 * ff)
+        self.logits, self.next_ids, self.out_ids = z(B, m.vocab, dtype=torch.float32), z(B, dtype=torch.int64), z(B, max_new, dtype=torch.int64)
+        self.tok32, self.state, self.desc, self.pos = (z(*sh, dtype=torch.int32) for sh in ((B,), (4,), (B, 8), (B,)))
+        # the MFMA weight streams (bf16 and 4-bit alike) read x from L2 with prologue 0: norm / SwiGLU run once, not once per block (pays from batch 4)
+        self.batched = fmt.stages and B >= 4
+        if self.batched:
+            self.hn, self.actb = z(B, d), z(B, ff)
+        fmt.buffers(self)
+        self.ad = {}   # (layer, group) -> (A [KP, in], Bfull [out_total, KP], R rows in use, r, fout) of the adapted groups
+        for gname, G in (lora.groups.items() if lora is not None else ()):
+            # blocks of r columns need 16-B lane loads; any other rank runs the dense form over the padded rows (their A rows and B columns are zero)
+            R, r_up, fo = (lora.r * len(G["projs"]), lora.r, G["fout"]) if lora.r % 8 == 0 else (G["KP"], G["KP"], G["out_total"])
+            if R > 768:
+                raise ValueError(f'adapters="live": group {gname!r} stacks {R} adapter rows, the decode kernels take at most 768 - use adapters="merged"')
+            if hk.lora_down_lds_bytes(B, G["fin"], R) > hk.LORA_DOWN_MAX_LDS:   # the rule of lhrs_lora_down, applied before anything is enqueued or captured
+                raise ValueError(f'adapters="live": a K-slice of group {gname!r} (K = {G["fin"]}, {R} adapter rows) for {B} rows does not fit the LDS - '
+                                 'use adapters="merged"')
+            for li in range(len(m.p["layers"])):
+                self.ad[(li, gname)] = (lora.view(lora.shadow, li, gname, "A"), lora.derived[(li, gname, "Bfull")], R, r_up, fo)
+        if self.ad:
+            self.acc = z(B, max(3 * d, 2 * ff), dtype=torch.float32)
+            self.tpart = z(hk.LORA_DOWN_MAX_SLICES * B * max(a[2] for a in self.ad.values()), dtype=torch.float32)
+        # split-context attention: 128-key slices, one workgroup each (32 * nsplit CUs); LHRS_DECODE_SPLIT=0 keeps one workgroup per head (A/B runs)
+        self.nsplit = min(16, -(-max_ctx // 128)) if os.environ.get("LHRS_DECODE_SPLIT", "1") != "0" else 1
+        self.attn_part = self.attn_tickets = self.attn_cs = None
+        if self.nsplit > 1 and m.hd == 128:
+            self.attn_part, self.attn_tickets = z(B, m.heads, self.nsplit, 132, dtype=torch.float32), z(B, m.heads, dtype=torch.int32)
+            self.attn_cs = z(B, 128, dtype=torch.float32)   # cos | sin of the new position, written by decode_advance
+
+    def staged(self, x, pro, norm_w):
+        """the batched path's materialised activation (RMSNorm / SwiGLU run once into hn / actb, the linear then has no prologue)"""
+        if self.batched and pro == hk.PRO_RMSNORM:
+            hk.rmsnorm_fwd(x, norm_w, self.m.eps, out=self.hn)
+            return self.hn, hk.PRO_NONE, None
+        if self.batched and pro == hk.PRO_SWIGLU:
+            hk.swiglu_fwd(x, self.m.ff, out=self.actb)
+            return self.actb, hk.PRO_NONE, norm_w
+        return x, pro, norm_w
+
+    def quantised(self, x, K, pro, norm_w):
+        """batch > 2 on e4m3 activations: the quantising producer of the prologue -> (e4m3 rows, per-row scales) in x8 / a8"""
+        if pro == hk.PRO_RMSNORM:
+            return hk.rmsnorm_fwd_q(x, norm_w, self.m.eps, want_bf16=False, q_out=self.x8)[1]
+        if pro == hk.PRO_SWIGLU:
+            return hk.swiglu_fwd_q(x, self.m.ff, q_out=self.a8)[1:]
+        # K = ff: the materialised SwiGLU of the batched live-adapter path (MXFP4); fp8 never stages, so its prologue-free linears have K = d
+        return hk.quant_fp8_rows(x, out=self.x8 if K == self.m.d else self.a8)
+
+    def lin(self, fmt, L, name, x, out, K, pro=hk.PRO_NONE, norm_w=None, residual=None, out_f32=False, adapter=None):
+        """out = pro(x) L[name]^T (+ residual) in weight format `fmt`, with the adapters of the linear's group around the base product"""
+        w, sc = fmt.weight(L, name, self.packed16)
+        if adapter is None:
+            return fmt.linear(self, w, sc, x, out, K, pro, norm_w, residual=residual, out_f32=out_f32)
+        x, pro, norm_w = self.staged(x, pro, norm_w)   # once, for the adapter and the base alike (base() then finds no prologue left)
+        A, Bfull, R, r_up, fo = adapter
+        acc = self.acc[:, :out.shape[1]]
+        nsl = hk.lora_down(x, A, self.tpart, K, R, prologue=pro, norm_w=norm_w, eps=self.m.eps)
+        fmt.linear(self, w, sc, x, acc, K, pro, norm_w, residual=None, out_f32=True)
+        hk.lora_up(acc, self.tpart, nsl, self.lora.s, Bfull, r_up, fo, out, residual=residual, R=R)
+
+    def attend(self, cache):
+        """RoPE of the new q / k, KV append and attention over the cache: qkv -> o"""
+        m, B, H, hd, max_ctx, scale = self.m, self.B, self.m.heads, self.m.hd, self.max_ctx, 1.0 / math.sqrt(self.m.hd)
+        kc, vc = cache[:2]
+        if self.kv8:  # kv_cache="fp8": the same launch on e4m3 codes + scale bytes, the new rows quantised as they are appended
+            hk.decode_attn_kv8(self.qkv, kc, vc, cache[2], cache[3], m.cos, m.sin, self.pos, self.o, B, H, hd, max_ctx, scale, self.nsplit,
+                               self.attn_part, self.attn_tickets, key_mask=self.kmask, cs=self.attn_cs)
+        elif hd == 128 and self.nsplit > 1:  # RoPE + KV append + attention over the cache in one launch, context split over workgroups
+            hk.decode_attn_split(self.qkv, kc, vc, m.cos, m.sin, self.pos, self.o, B, H, hd, max_ctx, scale, self.nsplit, self.attn_part,
+                                 self.attn_tickets, key_mask=self.kmask, cs=self.attn_cs)
+        elif hd == 128:
+            hk.decode_attn(self.qkv, kc, vc, m.cos, m.sin, self.pos, self.o, B, H, hd, max_ctx, scale, key_mask=self.kmask)
+        else:
+            hk.rope_kv_append(self.qkv, kc, vc, m.cos, m.sin, self.pos, B, H, hd, max_ctx)
+            hk.attn_fwd(self.qkv[:, :m.d], kc, vc, self.o, None, self.desc, B, H, hd, 1, 1 << 30, 64, True, scale, key_mask=self.kmask)
+
+    def enqueue(self):
+        """the step: token ids in tok32 -> fp32 logits"""
+        m, fmt, d, ad = self.m, self.fmt, self.m.d, self.ad
+        hk.decode_advance(self.state, self.desc, self.pos, self.B, self.max_ctx, 1, m.cos, m.sin, self.attn_cs)
+        hk.gather_rows(m.p["embed"], self.tok32, out=self.x)
+        x, x2 = self.x, self.x2
+        for li, (L, cache) in enumerate(zip(m.p["layers"], self.caches)):
+            self.lin(fmt, L, "qkv_w", x, self.qkv, d, hk.PRO_RMSNORM, L["ln1_w"], adapter=ad.get((li, "qkv")))
+            self.attend(cache)
+            self.lin(fmt, L, "o_w", self.o, x2, d, residual=x, adapter=ad.get((li, "o")))
+            self.lin(fmt, L, "gu_w", x2, self.gu, d, hk.PRO_RMSNORM, L["ln2_w"], adapter=ad.get((li, "gu")))
+            self.lin(fmt, L, "down_w", self.gu, x, m.ff, hk.PRO_SWIGLU, residual=x2, adapter=ad.get((li, "down")))
+        self.lin(self.head, m.p, "lm_head", x, self.logits, d, hk.PRO_RMSNORM, m.p["norm_w"], out_f32=True)
+
+
+# ------------------------------------------------------------------------------------------------- the token loops
+def warp_logits(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None) -> torch.Tensor:
+    """HF `generate(do_sample=True)`'s score processing before the multinomial draw, in HF's order: Temperature -> TopK -> TopP LogitsWarper
+    (cli_qa.py:176-186 passes temperature, the Llama-2 generation config top-k / top-p).  fp32 logits [B, V] in, filtered (-inf) logits out, on
+    whatever device they live; pinned to the HF classes by tests/test_host_cpu.py::test_sampling_warpers_match_hf."""
+    z = logits / max(float(temperature), 1e-6)
+    if top_k:
+        k = min(int(top_k), z.shape[-1])
+        kth = torch.topk(z, k, dim=-1).values[:, -1:]
+        z = z.masked_fill(z < kth, float("-inf"))
+    if top_p is not None and top_p < 1.0:
+        sz, si = torch.sort(z, descending=False, dim=-1)
+        cp = torch.softmax(sz, -1).cumsum(-1)
+        rm = cp <= (1 - top_p)
+        rm[:, -1] = False  # keep at least the most likely token
+        z = z.masked_fill(rm.scatter(1, si, rm), float("-inf"))
+    return z
+
+
+def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p=None, top_k=None,
+                  max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id=None, return_logits=False,
+                  use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1, length_penalty=1.0,
+                  early_stopping=False, return_beam_scores=False, num_return_sequences=1, live_lora=False, kv_cache="bf16", **_kw):
+    """TextModal.generate (text_modal.py:528-627): prefill over the spliced embeddings, then one token at a time with a KV cache; returns only
+    the NEW token ids [B, n_new] (HF generate started from inputs_embeds).  Greedy (the evaluation scripts' mode) runs entirely in HIP kernels;
+    with do_sample=True the fp32 logits go through HF's temperature / top-k / top-p warpers and one multinomial draw per token.  The step is a
+    captured hipGraph over static buffers (batch <= 16); without eos / stopping criteria / streamer the host never synchronises inside the loop.
+
+    sampler="device" (with do_sample=True) replaces the warpers and `torch.multinomial` by ONE launch of `hk.sample_rows` per token, between the
+    graph replay and `decode_emit`: same distribution as HF, drawn by Philox from (`seed`, step, row); `seed=None` takes `torch.initial_seed()`.
+    `repetition_penalty != 1` (HF RepetitionPenaltyLogitsProcessor over the tokens generated so far in this call) exists in that kernel only
+    and routes every pick through it whatever `sampler` says: mode 0 when sampling, mode 1 (first maximum of the penalised logits) when greedy.
+    With `eos_token_id` set the pad replacement of finished rows and the host's check still run between the pick and `decode_emit`; the kernel
+    has then already set the drawn token's bit in the seen bitmap of a finished row, which nothing reads any more."""
+    if sampler not in ("torch", "device"):
+        raise ValueError(f"sampler={sampler!r}: expected 'torch' or 'device'")
+    if int(num_beams) != 1:
+        return m._generate_beam(input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer,
+                                eos_token_id, return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty,
+                                early_stopping, return_beam_scores, num_return_sequences, live_lora, kv_cache)
+    m._check_kv_cache(kv_cache, int(input_ids.shape[0]))
+    pen = float(repetition_penalty)
+    device_pick = (sampler == "device" and do_sample) or pen != 1.0
+    if streamer is not None and getattr(streamer, "skip_prompt", False):
+        streamer.put(input_ids.cpu())  # transformers.TextStreamer protocol: the first put() is the prompt, which skip_prompt drops
+    embeds, _, mask, _ = m.prepare_inputs_for_multimodal(input_ids, attention_mask, None, image_embedding)
+    B, S0, d = embeds.shape
+    max_ctx, kmask = decode_context(m, mask, B, S0, max_new_tokens)
+    caches = m._alloc_kv(B * max_ctx, kv_cache)
+    dev, lora = m.device, m.lora if live_lora else None   # adapters="live": the store the session and the GEMM steps read
+    s, seen, step_dev = None, None, None
+
+    def session():
+        s = m._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora, kv_cache)
+        s.state[0], s.state[1] = S0, 0
+        return s
+
+    if device_pick:
+        seed = int(torch.initial_seed() if seed is None else seed)
+        if pen != 1.0:  # bitmap of the tokens generated so far in this call (HF started from inputs_embeds: the prompt is not in it)
+            seen = torch.zeros((B, (m.vocab + 31) // 32), device=dev, dtype=torch.int32)
+        if B <= 16:  # the draw's step counter is the session's count of emitted tokens, on the device
+            s = session()
+            step_dev = s.state[1:2]
+
+    def pick_device(logits, out=None, step_host=0):
+        return hk.sample_rows(logits, out, mode=0 if do_sample else 1, temperature=temperature, top_k=top_k, top_p=top_p,
+                              repetition_penalty=pen, seen=seen, seed=seed, step_dev=step_dev, step_host=step_host)
+
+    def pick(logits):
+        if device_pick:
+            return pick_device(logits, None if s is None else s.next_ids, 0 if s is not None else n_done)
+        if not do_sample:
+            return hk.argmax_rows(logits)
+        return torch.multinomial(torch.softmax(warp_logits(logits, temperature, top_k, top_p), -1), 1).squeeze(1)
+
+    # ---- prefill (GEMM path) -> logits of the last prompt position -> first new token
+    logits = gemm_logits(m, embeds.reshape(B * S0, d), B, S0, 0, caches, max_ctx, kv_cache == "fp8", kmask, lora, weights)
+    all_logits = [logits.clone()] if return_logits else []
+    n_done = 0
+    nxt = pick(logits)
+
+    host_checks = eos_token_id is not None or stopping_criteria is not None or streamer is not None
+    finished = torch.zeros(B, dtype=torch.bool, device=dev)
+
+    def host_step(ids_so_far, lg):  # -> stop?
+        nonlocal finished
+        if streamer is not None:
+            streamer.put(ids_so_far[:, -1].cpu())
+        if eos_token_id is not None:
+            finished |= ids_so_far[:, -1] == eos_token_id
+            if bool(finished.all()):
+                return True
+        return stopping_criteria is not None and any(c(ids_so_far, lg) for c in stopping_criteria)
+
+    n_done = 1
+    if B <= 16:
+        if s is None:
+            s = session()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            if nxt is not s.next_ids:
+                s.next_ids.copy_(nxt)
+            hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, B, max_new_tokens)
+            stop = host_checks and host_step(s.out_ids[:, :1], logits)
+            while not stop and n_done < max_new_tokens:
+                step_or_replay(s, s.enqueue, use_graph, n_done)
+                if return_logits:
+                    all_logits.append(s.logits.clone())
+                if device_pick:
+                    pick_device(s.logits, s.next_ids)
+                elif do_sample:
+                    s.next_ids.copy_(pick(s.logits))
+                else:
+                    hk.argmax_rows(s.logits, out=s.next_ids)
+                if eos_token_id is not None:
+                    s.next_ids.copy_(torch.where(finished, torch.full_like(s.next_ids, m.tokenizer.pad_token_id), s.next_ids))
+                hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, B, max_new_tokens)
+                n_done += 1
+                if host_checks:
+                    stop = host_step(s.out_ids[:, :n_done], s.logits)
+        torch.cuda.current_stream().wait_stream(side)
+        ids = s.out_ids[:, :n_done].clone()
+    else:
+        out_ids = [nxt]
+        stop = host_checks and host_step(torch.stack(out_ids, 1), logits)
+        while not stop and n_done < max_new_tokens:
+            x = hk.gather_rows(m.p["embed"], out_ids[-1].clamp(0, m.vocab - 1).to(torch.int32))
+            logits = gemm_logits(m, x, B, 1, S0 + n_done - 1, caches, max_ctx, False, kmask, lora, weights)
+            if return_logits:
+                all_logits.append(logits.clone())
+            nxt = pick(logits)
+            if eos_token_id is not None:
+                nxt = torch.where(finished, torch.full_like(nxt, m.tokenizer.pad_token_id), nxt)
+            out_ids.append(nxt)
+            n_done += 1
+            if host_checks:
+                stop = host_step(torch.stack(out_ids, 1), logits)
+        ids = torch.stack(out_ids, 1)
+    if streamer is not None:
+        streamer.end()
+    return (ids, torch.stack(all_logits, 1)) if return_logits else ids
+
+
+def generate_beam(m, input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer, eos_token_id,
+                  return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty, early_stopping, return_beam_scores,
+                  num_return_sequences, live_lora=False, kv_cache="bf16"):
+    """Deterministic beam search, HF `generate(num_beams=nb, do_sample=False)` (generation/utils.py _beam_search): the prompt is prefilled ONCE per
+    batch row into cache row b * nb and replicated to the row's other beams by `hk.kv_beam_reorder`; every further token is one single-stream
+    graph of [model step over B * nb rows, beam_topk_rows, beam_step, kv_beam_reorder, decode_emit] (csrc/beam.hip).  All bookkeeping lives on
+    the device; the host reads the batch-wide `done` word every fourth token when an EOS is set (once done, the kernels change nothing) and never
+    without one.  -> ids [B, L] of each row's best hypothesis, pad_token_id past its end (, logits [B * nb, n, V])(, scores [B])."""
+    nb = int(num_beams)
+    for bad, why in ((nb < 1, f"num_beams={num_beams!r}: must be >= 1"),
+                     (do_sample, "do_sample=True with num_beams > 1 (beam-multinomial sampling) is not implemented"),
+                     (streamer is not None, "streamer is not supported with num_beams > 1 (HF: beam search has no token stream)"),
+                     (stopping_criteria is not None, "stopping_criteria is not supported with num_beams > 1: stopping is eos_token_id / max_new_tokens, on the device"),
+                     (int(num_return_sequences) != 1, f"num_return_sequences={num_return_sequences!r}: only the best hypothesis of each row is returned"),
+                     (early_stopping not in (False, True), f"early_stopping={early_stopping!r}: False or True ('never' is not implemented)")):
+        if bad:
+            raise ValueError(why)
+    m._check_kv_cache(kv_cache, int(input_ids.shape[0]) * nb, nb)
+    embeds, _, mask, _ = m.prepare_inputs_for_multimodal(input_ids, attention_mask, None, image_embedding)
+    B, S0, d = embeds.shape
+    R = B * nb
+    if nb > 8 or R > 16:
+        raise ValueError(f"num_beams={nb} with batch {B}: batch * num_beams must be <= 16 (and num_beams <= 8)")
+    V, dev, pen = m.vocab, m.device, float(repetition_penalty)
+    max_ctx, kmask = decode_context(m, mask, B, S0, max_new_tokens)   # left-padded prompts, as in generate_rows; every beam hides its row's padding
+    kmask_r = None if kmask is None else kmask.repeat_interleave(nb, 0).contiguous()
+    caches = m._alloc_kv(R * max_ctx, kv_cache)
+    kv8, lora = kv_cache == "fp8", m.lora if live_lora else None
+    s = m._decode_session(R, max_ctx, caches, max_new_tokens, weights, kmask_r, lora, kv_cache)
+    s.state[0], s.state[1] = S0, 0
+    st = hk.BeamState(B, nb, V, max_new_tokens, length_penalty, dev)
+    # kv_beam_reorder is a byte copy in 16-byte chunks whose `d` counts 2-byte units: the bf16 caches with d, the kv8 code caches with d / 2
+    # and the scale arrays with H / 2 - codes and scales move together, in two launches
+    tables = [(hk.kv_cache_table(caches, dev), d)] if not kv8 else [(hk.kv_cache_table([c[:2] for c in caches], dev), d // 2),
+                                                                    (hk.kv_cache_table([c[2:] for c in caches], dev), m.heads // 2)]
+
+    # ---- prefill: sequence b into cache row b * nb (a cache "row" of nb * max_ctx positions), logits of the last prompt position
+    logits = gemm_logits(m, embeds.reshape(B * S0, d), B, S0, 0, caches, nb * max_ctx, kv8, kmask, lora, weights)
+    logits = logits.repeat_interleave(nb, 0).contiguous()   # the row's beams all start from it
+    all_logits = [logits] if return_logits else []
+
+    def beam_tail(lg, t0, t1):
+        hk.beam_topk_rows(lg, st, pen)
+        hk.beam_step(st, s.next_ids, eos_token_id, early_stopping)
+        for table, units in tables:
+            hk.kv_beam_reorder(table, B, nb, max_ctx, units, st.parent, t0, t1, S0 if t0 == 0 else max_new_tokens, done=st.bstate[1:2])
+        hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, R, max_new_tokens)
+
+    def step():
+        s.enqueue()
+        beam_tail(s.logits, S0, s.state[0:1])
+
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        beam_tail(logits, 0, S0)          # parents are all 0: replicates the prompt's cache to every beam of the row
+        n_done = 1
+        while n_done < max_new_tokens:
+            step_or_replay(s, step, use_graph, n_done)
+            if return_logits:
+                all_logits.append(s.logits.clone())
+            n_done += 1
+            if eos_token_id is not None and n_done % 4 == 0 and int(st.bstate[1].item()):
+                break
+    torch.cuda.current_stream().wait_stream(side)
+    # ---- the result of each row: its best finished hypothesis, else its best running beam (tiny host-side epilogue, once per call)
+    n = int(st.bstate[0].item())
+    fin_score, fin_len, fin_slot = st.fin_score.view(B, nb).cpu(), st.fin_len.view(B, nb).cpu(), st.fin_slot.view(B, nb).cpu()
+    fin_seq, hist, run = st.fin_seq.view(B, nb, -1).cpu(), st.hist[n & 1].view(B, nb, -1).cpu(), st.run_score.view(B, nb).cpu()
+    rows, scores = [], []
+    for b in range(B):
+        if int(fin_len[b, 0]) > 0:
+            rows.append(fin_seq[b, int(fin_slot[b, 0]), :int(fin_len[b, 0])])
+            scores.append(float(fin_score[b, 0]))
+        else:
+            rows.append(hist[b, 0, :n])
+            scores.append(float(run[b, 0]))
+    ids = torch.full((B, max(len(r) for r in rows)), int(m.tokenizer.pad_token_id), dtype=torch.int64)
+    for b, r in enumerate(rows):
+        ids[b, :len(r)] = r
+    out = (ids.to(dev),)
+    if return_logits:
+        out += (torch.stack(all_logits[:n], 1),)
+    if return_beam_scores:
+        out += (torch.tensor(scores, dtype=torch.float32, device=dev),)
+    return out if len(out) > 1 else out[0]

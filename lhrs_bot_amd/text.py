@@ -17,7 +17,8 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import kernels as hk
+from . import generation, kernels as hk
+from .generation import warp_logits  # noqa: F401  (callers import it from here)
 
 IGNORE_INDEX = -100
 IMAGE_TOKEN_INDEX = -200
@@ -72,25 +73,6 @@ class SyntheticTokenizer:
 LORA_GROUPS = {  # fused GEMM group -> (sub-projections, in_features, out_features per projection)
     "qkv": (("q", "k", "v"), 4096, 4096), "o": (("o",), 4096, 4096), "gu": (("gate", "up"), 4096, 11008), "down": (("down",), 11008, 4096)}
 LORA_ALL = ("q", "k", "v", "o", "gate", "up", "down")  # find_all_linear_names: every nn.Linear except lm_head (text_modal.py:658-667)
-
-
-def warp_logits(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None) -> torch.Tensor:
-    """The score processing HF `generate(do_sample=True)` applies before its multinomial draw, in HF's order: TemperatureLogitsWarper ->
-    TopKLogitsWarper -> TopPLogitsWarper (transformers generation/logits_process.py; cli_qa.py:176-186 passes temperature, the Llama-2
-    generation config top-k / top-p).  fp32 logits [B, V] in, filtered (-inf) logits out; pinned to the HF classes by
-    tests/test_host_cpu.py::test_sampling_warpers_match_hf.  Runs on whatever device the HIP-computed logits live on."""
-    z = logits / max(float(temperature), 1e-6)
-    if top_k:
-        k = min(int(top_k), z.shape[-1])
-        kth = torch.topk(z, k, dim=-1).values[:, -1:]
-        z = z.masked_fill(z < kth, float("-inf"))
-    if top_p is not None and top_p < 1.0:
-        sz, si = torch.sort(z, descending=False, dim=-1)
-        cp = torch.softmax(sz, -1).cumsum(-1)
-        rm = cp <= (1 - top_p)
-        rm[:, -1] = False  # keep at least the most likely token
-        z = z.masked_fill(rm.scatter(1, si, rm), float("-inf"))
-    return z
 
 
 class LoraStore:
@@ -261,12 +243,11 @@ class TextModal:
         lo = self.lora
         if lo is None:
             return
-        wname = {"qkv": "qkv_w", "o": "o_w", "gu": "gu_w", "down": "down_w"}
         for li, L in enumerate(self.p["layers"]):
             for gname in lo.groups:
-                W = L[wname[gname]]
+                W = L[gname + "_w"]
                 hk.gemm_nt(lo.derived[(li, gname, "Bfull")], lo.derived[(li, gname, "AT")], out=W, residual=W, alpha=lo.s)
-                L[wname[gname] + "T"] = hk.transpose(W)
+                L[gname + "_w" + "T"] = hk.transpose(W)
             self._drop_derived(L)
         requant = "e4m3" if self.base8 else ("int8" if self.base_int8 else None)
         base4 = getattr(self, "base4", None)
@@ -277,7 +258,8 @@ class TextModal:
             self.quantize_base(4, quant_type=base4[0], double_quant=base4[1])   # peft re-quantises a merged Linear4bit the same way
 
     _W4_PARTS = {"qkv_w": 3, "o_w": 1, "gu_w": 2, "down_w": 1}   # reference Linears per fused weight (row-concatenated): 4-bit statistics are per Linear
-    DERIVED_SUFFIXES = ("p", "8", "8s", "8p", "i8", "i8s", "i8p", "q4", "4p", "mx4")   # decode re-tilings and e4m3 copies of a weight `<name>` / `<name>T`, rebuilt lazily from it
+    # rebuilt from a weight `<name>` / `<name>T`: the decode operands of generation.FORMATS + e4m3 copies, int8 rows and factors, 4-bit states
+    DERIVED_SUFFIXES = generation.DECODE_SUFFIXES + ("8", "8s", "i8", "i8s", "q4")
 
     def _drop_derived(self, L) -> None:
         """Forget every tensor that was computed FROM a decoder weight of layer dict `L` (decode re-tilings, e4m3 copies): after the weight
@@ -726,108 +708,47 @@ class TextModal:
 
     __call__ = decode
 
-    # ------------------------------------------------------------------ generate (KV cache)
-    def _layer_step(self, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None, int8=False):
-        """One decoder layer over S_new new positions per sequence with `ctx` cached positions (prefill: ctx = 0).  li = the layer's index:
-        generate(adapters="live") - every adapted group runs its adapters through the training forward (`_lin` / `_gu_fwd`: gemm_nt_skinny, then
-        the base GEMM with the (T, Bfull) pair on its accumulators) on the bf16 base weights; the caller has switched dropout off.
-        int8 (generate(weights="int8") only, li given): the four linears are the LLM.int8 products of the training forward (`hk.int8_linear` on
-        the int8 rows), the adapters of a live store on top."""
-        d, H, hd, ff = self.d, self.heads, self.hd, self.ff
-        M = x.shape[0]
-        i8 = (lambda name: (L[name + "i8"], L[name + "i8s"])) if int8 else (lambda name: None)
-        h = hk.rmsnorm_fwd(x, L["ln1_w"], self.eps)
-        if li is None:
-            qkv = hk.gemm_rope_fwd(h, L["qkv_w"], self.cos, self.sin, pos_mod=S_new, pos0=ctx, rope_cols=2 * d, head_dim=hd)
-        else:
-            qkv = self._lin(li, "qkv", h, L["qkv_w"], rope=(S_new, ctx), i8=i8("qkv_w"))
-        o = torch.empty((M, d), device=self.device, dtype=torch.bfloat16)
-        if len(cache) == 4:
-            # kv_cache="fp8", prefill only: attention reads the exact bf16 K / V of the prompt straight out of `qkv` (desc: kv_off = b * S_new),
-            # so the prompt's logits are those of the bf16-cache mode bit for bit; the rows enter the cache as codes + scale bytes
-            assert ctx == 0, "the kv8 cache has no multi-row step after the prefill (generate() rejects batch > 16)"
-            kc8, vc8, ks, vs = cache
-            hk.attn_fwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True,
-                        1.0 / math.sqrt(hd), key_mask=kmask)
-            for b in range(B):
-                rows = qkv[b * S_new:(b + 1) * S_new]
-                hk.kv8_quant_rows(rows[:, d:2 * d], kc8, ks, b * max_ctx, H)
-                hk.kv8_quant_rows(rows[:, 2 * d:], vc8, vs, b * max_ctx, H)
-        else:
-            kc, vc = cache
-            row_b = d * 2
-            for b in range(B):  # append the new K / V rows of sequence b at position ctx of its cache
-                src = qkv.data_ptr() + b * S_new * 3 * row_b
-                hk.copy_2d(kc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + row_b, 3 * row_b, row_b, S_new)
-                hk.copy_2d(vc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + 2 * row_b, 3 * row_b, row_b, S_new)
-            hk.attn_fwd(qkv[:, :d], kc, vc, o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True, 1.0 / math.sqrt(hd), key_mask=kmask)
-        if li is not None:
-            x = self._lin(li, "o", o, L["o_w"], residual=x, i8=i8("o_w"))
-            h = hk.rmsnorm_fwd(x, L["ln2_w"], self.eps, out=h)
-            _, act, _ = self._gu_fwd(li, h, L["gu_w"], None, i8=i8("gu_w"))
-            return self._lin(li, "down", act, L["down_w"], residual=x, i8=i8("down_w"))
-        x = hk.gemm_nt(o, L["o_w"], residual=x)
-        h = hk.rmsnorm_fwd(x, L["ln2_w"], self.eps, out=h)
-        act = hk.swiglu_fwd(hk.gemm_nt(h, L["gu_w"]), ff)
-        return hk.gemm_nt(act, L["down_w"], residual=x)
+    # ------------------------------------------------------------------ generate (KV cache): generation.py, bound here so that callers go through the model
+    _layer_step, _check_kv_cache, _alloc_kv = generation.layer_step, generation.check_kv_cache, generation.alloc_kv
+    _generate, _generate_beam = generation.generate_rows, generation.generate_beam
+
+    def _decode_session(self, B, max_ctx, caches, max_new, weights="bf16", kmask=None, lora=None, kv_cache="bf16"):
+        return generation.DecodeSession(self, B, max_ctx, caches, max_new, weights, kmask, lora, kv_cache)
 
     def quantize_fp8(self):
         """e4m3 copies (per-output-row scale) of every LLaMA linear for the decode step: 6.7 GB instead of 13.5 GB per token."""
-        for L in self.p["layers"]:
-            for k in ("qkv_w", "o_w", "gu_w", "down_w"):
-                L[k + "8"], L[k + "8s"] = hk.quant_fp8_rows(L[k])
-        self.p["lm_head8"], self.p["lm_head8s"] = hk.quant_fp8_rows(self.p["lm_head"])
+        generation.quantize_fp8(self)
 
     def pack_fp8_decode(self):
         """Decode-only copies of the e4m3 weights in the MFMA GEMV's operand order (hk.repack_fp8_mfma): the batch-1 weight stream then
         reads consecutive 1-KiB lines instead of 64-B segments of 16 strided rows (+6.7 GB of HBM next to the row-major copies that
         the prefill / training GEMMs use)."""
-        if "qkv_w8" not in self.p["layers"][0]:
-            self.quantize_fp8()
-        for L in self.p["layers"]:
-            for k in ("qkv_w", "o_w", "gu_w", "down_w"):
-                L[k + "8p"] = hk.repack_fp8_mfma(L[k + "8"])
-        self.p["lm_head8p"] = hk.repack_fp8_mfma(self.p["lm_head8"])
+        generation.FORMATS["fp8"].pack(self)
 
     def pack_bf16_decode(self):
         """Decode-only copies of the bf16 weights in the batched MFMA GEMV's operand order (hk.repack_bf16_mfma; +13.5 GB of HBM): from
         batch 2 the shared weight stream of generate() reads consecutive 1-KiB lines instead of 64-B segments of 16 strided rows."""
-        for L in self.p["layers"]:
-            for k in ("qkv_w", "o_w", "gu_w", "down_w"):
-                L[k + "p"] = hk.repack_bf16_mfma(L[k])
-        self.p["lm_headp"] = hk.repack_bf16_mfma(self.p["lm_head"])
+        generation.FORMATS["bf16"].pack(self)
 
     def pack4_decode(self):
         """Decode-only form of the 4-bit base (`weights="4bit"`): per fused weight the stored codes of its reference Linears side by side and
         their block statistics in fp32 (`hk.pack4_decode`: +3.6 GB next to the `q4` states; nothing is quantised anew).  lm_head is not
         quantised in the reference and has no 4-bit form."""
-        if not self.base4:
-            raise ValueError("pack4_decode: the decoder is not on the 4-bit base - call quantize_base(4, quant_type, double_quant) first")
-        for L in self.p["layers"]:
-            for k in self._W4_PARTS:
-                L[k + "4p"] = hk.pack4_decode(L[k + "q4"], *L[k].shape)
+        generation.FORMATS["4bit"].pack(self)
 
     def pack_mx4_decode(self):
         """Decode-only MXFP4 form of the decoder linears (`weights="mxfp4"`): whatever bf16 weight the decoder currently holds is quantised to
         OCP MXFP4 (`hk.quant_mx4_rows`: e2m1 codes, one e8m0 scale per 32 consecutive k) and re-tiled into the operand order of `hk.gemv_mx4`;
         only the tiled pair stays, under `L[name + "mx4"]` (+3.5 GB at full depth; the row-major temporaries of a weight are freed before the
         next one is made).  Lossy, like `quantize_fp8`.  lm_head has no MXFP4 form."""
-        for L in self.p["layers"]:
-            for k in ("qkv_w", "o_w", "gu_w", "down_w"):
-                codes, scales = hk.quant_mx4_rows(L[k])
-                L[k + "mx4"] = hk.repack_mx4_mfma(codes, scales)
-                del codes, scales
+        generation.FORMATS["mxfp4"].pack(self)
 
     def pack_int8_decode(self):
         """Decode-only copies of the int8 rows of the LLM.int8 base in the operand order of `hk.gemv_int8` (`hk.repack_int8_mfma`), under
         `L[name + "i8p"]` (+6.7 GB at full depth next to the row-major rows that the prefill and training products read): the single-token
         weight stream then reads consecutive 1-KiB lines.  The codes are the base's own; nothing is quantised anew.  lm_head is not
         quantised in the reference and has no int8 form."""
-        if not self.p["layers"] or "qkv_wi8" not in self.p["layers"][0]:
-            raise ValueError('pack_int8_decode: the decoder is not on the LLM.int8 base - call quantize_base(8, "int8") first')
-        for L in self.p["layers"]:
-            for k in ("qkv_w", "o_w", "gu_w", "down_w"):
-                L[k + "i8p"] = hk.repack_int8_mfma(L[k + "i8"])
+        generation.FORMATS["int8"].pack(self)
 
     def quantize_base(self, bits: int = 8, scheme: str = "e4m3", quant_type: str = "nf4", double_quant: bool = True):
         """`bits: 8` of Config/multi_modal_stage{2,3}.yaml (text_modal.py:91-131: the reference loads the frozen LLaMA through bitsandbytes
@@ -889,220 +810,6 @@ class TextModal:
         self.base8, self.base_int8 = True, False
         return self
 
-    def _check_kv_cache(self, kv_cache, rows, num_beams=1):
-        """generate(kv_cache=...): "bf16" or "fp8" (the kv8 format of csrc/decode_kv8.hip); what "fp8" cannot serve raises here, before anything is
-        allocated or enqueued.  rows = batch * num_beams."""
-        if kv_cache not in ("bf16", "fp8"):
-            raise ValueError(f"kv_cache={kv_cache!r}: expected 'bf16' or 'fp8'")
-        if kv_cache == "bf16":
-            return
-        if self.hd != 128:
-            raise ValueError(f'kv_cache="fp8" needs head_dim 128 (one scale byte per 128-value head row), this model has head_dim {self.hd}')
-        if rows > 16:
-            raise ValueError(f'kv_cache="fp8" with batch (x num_beams) {rows} > 16: beyond 16 rows the single-token step attends through attn_fwd '
-                             'over bf16 caches, which the fp8 cache does not have')
-        if num_beams > 1 and self.heads % 16:
-            raise ValueError(f'kv_cache="fp8" with num_beams > 1 needs a head count that is a multiple of 16 (kv_beam_reorder moves the scale '
-                             f'bytes of a position in 16-byte chunks), this model has {self.heads} heads')
-
-    def _alloc_kv(self, rows, kv_cache):
-        """per layer: (K, V) bf16 [rows, d], or for kv_cache="fp8" (K codes, V codes uint8 [rows, d], K scales, V scales uint8 [rows, H])"""
-        dev, d, H, n = self.device, self.d, self.heads, len(self.p["layers"])
-        if kv_cache == "fp8":
-            return [(torch.empty((rows, d), device=dev, dtype=torch.uint8), torch.empty((rows, d), device=dev, dtype=torch.uint8),
-                     torch.empty((rows, H), device=dev, dtype=torch.uint8), torch.empty((rows, H), device=dev, dtype=torch.uint8)) for _ in range(n)]
-        return [(torch.empty((rows, d), device=dev, dtype=torch.bfloat16), torch.empty((rows, d), device=dev, dtype=torch.bfloat16)) for _ in range(n)]
-
-    def _decode_session(self, B, max_ctx, caches, max_new, weights="bf16", kmask=None, lora=None, kv_cache="bf16"):
-        """Static buffers + one captured hipGraph for the single-token step (batch <= 16): embedding gather, 32 x [RMSNorm,
-        QKV GEMV, RoPE, KV append, attention over the cache, O GEMV + residual, RMSNorm, gate|up GEMV, SwiGLU, down GEMV +
-        residual], final norm, lm_head GEMV -> fp32 logits.  Context length / positions live on the device
-        (decode_advance), so the graph is captured once and replayed for every token.
-
-        lora = a LoraStore (generate(adapters="live")): a linear whose fused group carries adapters becomes three launches on the same stream -
-        `hk.lora_down` on the activation the base product sees, the GEMV of whatever weight format into the fp32 `s.acc` without its residual,
-        `hk.lora_up` into the linear's output with the residual: y = bf16(x W^T + (s x A^T) B^T + residual) on one fp32 value, what training's
-        `_lin` computes.  The session reads the store's bf16 shadow and `Bfull` in place (`LoraStore.refresh` rewrites their storage), so it
-        holds no copy of an adapter; un-adapted groups and lm_head launch exactly what they launch without a store.
-
-        kv_cache="fp8": `caches` holds (K codes, V codes, K scale bytes, V scale bytes) per layer (`_alloc_kv`), and the attention of the step is
-        `hk.decode_attn_kv8` - one launch, like the bf16 kernels, with the same `nsplit`."""
-        dev, d, ff, H, hd, V = self.device, self.d, self.ff, self.heads, self.hd, self.vocab
-        self._check_kv_cache(kv_cache, B)
-        kv8 = kv_cache == "fp8"
-        bf = torch.bfloat16
-        s = types.SimpleNamespace()
-        s.B, s.max_ctx, s.max_new, s.caches = B, max_ctx, max_new, caches
-        s.x, s.x2, s.h, s.o = (torch.zeros((B, d), device=dev, dtype=bf) for _ in range(4))
-        s.qkv = torch.zeros((B, 3 * d), device=dev, dtype=bf)
-        s.gu = torch.zeros((B, 2 * ff), device=dev, dtype=bf)
-        s.act = torch.zeros((B, ff), device=dev, dtype=bf)
-        s.logits = torch.zeros((B, V), device=dev, dtype=torch.float32)
-        s.next_ids = torch.zeros(B, device=dev, dtype=torch.int64)
-        s.tok32 = torch.zeros(B, device=dev, dtype=torch.int32)
-        s.out_ids = torch.zeros((B, max_new), device=dev, dtype=torch.int64)
-        s.state = torch.zeros(4, device=dev, dtype=torch.int32)
-        s.desc = torch.zeros((B, 8), device=dev, dtype=torch.int32)
-        s.pos = torch.zeros(B, device=dev, dtype=torch.int32)
-        scale = 1.0 / math.sqrt(hd)
-
-        if weights not in ("bf16", "fp8", "4bit", "mxfp4", "int8"):
-            raise ValueError(f"weights={weights!r}: expected 'bf16', 'fp8', '4bit', 'mxfp4' or 'int8'")
-        fp8, w4, mx4, w8i = weights == "fp8", weights == "4bit", weights == "mxfp4", weights == "int8"
-        if w8i:  # the decoder linears stream the int8 rows of the LLM.int8 base (hk.int8_decode_prepare + hk.gemv_int8); lm_head stays bf16
-            if "qkv_wi8" not in self.p["layers"][0]:
-                raise ValueError('weights="int8" needs the LLM.int8 base: quantize_base(8, "int8") (YAML `bits: 8`)')
-            if d % 64 or ff % 64 or max(d, ff) > 16384:
-                raise ValueError(f'weights="int8" needs hidden sizes that are multiples of 64 (the MFMA step) and at most 16384, got {d} and {ff}')
-            if "qkv_wi8p" not in self.p["layers"][0]:
-                self.pack_int8_decode()
-            s.i8ws = hk.Int8DecodeWorkspace(dev, B, max(d, ff), self._i8ws.threshold if self._i8ws is not None else 6.0)
-        if fp8 and "qkv_w8p" not in self.p["layers"][0]:
-            self.pack_fp8_decode()
-        if w4:  # the decoder linears stream the 4-bit codes (hk.gemv4); lm_head is not quantised in the reference and stays bf16
-            if not self.base4:
-                raise ValueError('weights="4bit" needs the 4-bit base: quantize_base(4, quant_type, double_quant) (YAML `bits: 4`)')
-            if "qkv_w4p" not in self.p["layers"][0]:
-                self.pack4_decode()
-        if mx4:  # the decoder linears stream MXFP4 codes + block scales (hk.gemv_mx4) against the e4m3 activations of the fp8 mode; lm_head stays bf16
-            if d % 128 or ff % 128:
-                raise ValueError(f'weights="mxfp4" needs hidden sizes that are multiples of 128 (the MFMA step), got {d} and {ff}')
-            if "qkv_wmx4" not in self.p["layers"][0]:
-                self.pack_mx4_decode()
-
-        packed16 = not fp8 and B >= 2 and d % 128 == 0 and ff % 128 == 0  # batched bf16: the MFMA GEMV on re-tiled weights
-        if packed16 and (w4 or mx4 or w8i):  # lm_head alone: pack_bf16_decode() would add 13.5 GB of re-tiled decoder weights that this mode never reads
-            if "lm_headp" not in self.p:
-                self.p["lm_headp"] = hk.repack_bf16_mfma(self.p["lm_head"])
-        elif packed16 and "qkv_wp" not in self.p["layers"][0]:
-            self.pack_bf16_decode()
-
-        def W(L, name):  # (weight, per-row scale or None)
-            if w4:
-                return L[name + "4p"], None
-            if mx4:
-                return L[name + "mx4"], None
-            if w8i:
-                return L[name + "i8p"], L[name + "i8s"]
-            return (L[name + "8p"], L[name + "8s"]) if fp8 else (L[name + "p"] if packed16 else L[name], None)
-
-        # the MFMA weight streams (bf16 and 4-bit alike) read x from L2 with prologue 0: norm / SwiGLU run once, not once per block (pays from batch 4)
-        batched = B >= 4 and not fp8
-        if batched:
-            s.hn = torch.zeros((B, d), device=dev, dtype=bf)
-            s.actb = torch.zeros((B, ff), device=dev, dtype=bf)
-        if fp8 or mx4:  # e4m3 activations on the block-scaled MFMA: static e4m3 operand buffers (graph capture: no allocation)
-            s.x8 = (torch.zeros((B, d), device=dev, dtype=torch.uint8), torch.zeros(B, device=dev, dtype=torch.float32))
-            s.a8 = (torch.zeros((B, ff), device=dev, dtype=torch.uint8), torch.zeros(B, device=dev, dtype=torch.float32))
-
-        def staged(x_in, pro, norm_w):
-            """the batched path's materialised activation (RMSNorm / SwiGLU run once into s.hn / s.actb, the linear then has no prologue)"""
-            if batched and pro == hk.PRO_RMSNORM:
-                hk.rmsnorm_fwd(x_in, norm_w, self.eps, out=s.hn)
-                return s.hn, hk.PRO_NONE, None
-            if batched and pro == hk.PRO_SWIGLU:
-                hk.swiglu_fwd(x_in, ff, out=s.actb)
-                return s.actb, hk.PRO_NONE, norm_w
-            return x_in, pro, norm_w
-
-        def quantised(x_in, K, pro, norm_w):
-            """batch > 2 on e4m3 activations: the quantising producer of the prologue -> (e4m3 rows, per-row scales) in s.x8 / s.a8"""
-            if pro == hk.PRO_RMSNORM:
-                return hk.rmsnorm_fwd_q(x_in, norm_w, self.eps, want_bf16=False, q_out=s.x8)[1]
-            if pro == hk.PRO_SWIGLU:
-                return hk.swiglu_fwd_q(x_in, ff, q_out=s.a8)[1:]
-            # K = ff: the materialised SwiGLU of the batched live-adapter path (MXFP4).  `batched` excludes fp8, so a prologue-free fp8
-            # linear always has K = d and lands in s.x8
-            return hk.quant_fp8_rows(x_in, out=s.x8 if K == d else s.a8)
-
-        def base(w, sc, x_in, out, K, pro=hk.PRO_NONE, norm_w=None, residual=None, out_f32=False):
-            if fp8:  # up to batch 2 prologue + activation quantisation run inside the GEMV: five launches per layer
-                if B <= 2:
-                    hk.gemv_fp8_mfma_fused(w, sc, x_in, out, K, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
-                else:
-                    x8, sx = quantised(x_in, K, pro, norm_w)
-                    hk.gemv_fp8_mfma(w, sc, x8, sx, out, residual=residual, out_f32=out_f32)
-                return
-            if isinstance(w, hk.PackedMX4):   # as the fp8 branch
-                if B <= 2:
-                    hk.gemv_mx4_fused(w, x_in, out, K, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
-                else:
-                    x8, sx = quantised(x_in, K, pro, norm_w)
-                    hk.gemv_mx4(w, x8, sx, out, residual=residual, out_f32=out_f32)
-                return
-            if isinstance(w, hk.PackedI8):   # prologue, outlier split and quantisation in one launch, then the int8 weight stream
-                hk.int8_decode_prepare(x_in, K, s.i8ws, prologue=pro, norm_w=norm_w, eps=self.eps)
-                hk.gemv_int8(w, sc, s.i8ws, out, K, residual=residual, out_f32=out_f32)
-                return
-            x_in, pro, norm_w = staged(x_in, pro, norm_w)
-            if isinstance(w, hk.Packed4):
-                hk.gemv4(w, x_in, out, K, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
-                return
-            hk.gemv_fused(w, x_in, out, K, wscale=sc, prologue=pro, norm_w=norm_w, eps=self.eps, residual=residual, out_f32=out_f32)
-
-        ad = {}   # (layer, group) -> (A [KP, in], Bfull [out_total, KP], R rows in use, r, fout) of the adapted groups
-        if lora is not None and lora.groups:
-            for gname, G in lora.groups.items():
-                nproj = len(G["projs"])
-                # blocks of r columns need 16-B lane loads; any other rank runs the dense form over the padded rows (their A rows and B columns are zero)
-                R, r_up, fo = (lora.r * nproj, lora.r, G["fout"]) if lora.r % 8 == 0 else (G["KP"], G["KP"], G["out_total"])
-                if R > 768:
-                    raise ValueError(f'adapters="live": group {gname!r} stacks {R} adapter rows, the decode kernels take at most 768 - use adapters="merged"')
-                if hk.lora_down_lds_bytes(B, G["fin"], R) > hk.LORA_DOWN_MAX_LDS:   # the rule of lhrs_lora_down, applied before anything is enqueued or captured
-                    raise ValueError(f'adapters="live": a K-slice of group {gname!r} (K = {G["fin"]}, {R} adapter rows) for {B} rows does not fit the LDS - '
-                                     'use adapters="merged"')
-                for li in range(len(self.p["layers"])):
-                    ad[(li, gname)] = (lora.view(lora.shadow, li, gname, "A"), lora.derived[(li, gname, "Bfull")], R, r_up, fo)
-            s.acc = torch.zeros((B, max(3 * d, 2 * ff)), device=dev, dtype=torch.float32)
-            s.tpart = torch.zeros(hk.LORA_DOWN_MAX_SLICES * B * max(a[2] for a in ad.values()), device=dev, dtype=torch.float32)
-
-        def lin(w, sc, x_in, out, K, pro=hk.PRO_NONE, norm_w=None, residual=None, out_f32=False, adapter=None):
-            if adapter is None:
-                return base(w, sc, x_in, out, K, pro, norm_w, residual, out_f32)
-            x_in, pro, norm_w = staged(x_in, pro, norm_w)   # once, for the adapter and the base alike (base() then finds no prologue left)
-            A, Bfull, R, r_up, fo = adapter
-            acc = s.acc[:, :out.shape[1]]
-            nsl = hk.lora_down(x_in, A, s.tpart, K, R, prologue=pro, norm_w=norm_w, eps=self.eps)
-            base(w, sc, x_in, acc, K, pro, norm_w, None, True)
-            hk.lora_up(acc, s.tpart, nsl, lora.s, Bfull, r_up, fo, out, residual=residual, R=R)
-
-        # split-context attention (lhrs_decode_attn_split): 128-key slices, one workgroup each, so that a long context streams through
-        # 32 * nsplit CUs; LHRS_DECODE_SPLIT=0 keeps the one-workgroup-per-head kernel (A/B runs)
-        nsplit = min(16, -(-max_ctx // 128)) if os.environ.get("LHRS_DECODE_SPLIT", "1") != "0" else 1
-        if nsplit > 1 and hd == 128:
-            s.attn_part = torch.zeros((B, H, nsplit, 132), device=dev, dtype=torch.float32)
-            s.attn_tickets = torch.zeros((B, H), device=dev, dtype=torch.int32)
-            s.attn_cs = torch.zeros((B, 128), device=dev, dtype=torch.float32)   # cos | sin of the new position, written by decode_advance
-
-        def enqueue():
-            cs = getattr(s, "attn_cs", None)
-            hk.decode_advance(s.state, s.desc, s.pos, B, max_ctx, 1, self.cos, self.sin, cs)
-            hk.gather_rows(self.p["embed"], s.tok32, out=s.x)
-            x, x2 = s.x, s.x2
-            for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
-                lin(*W(L, "qkv_w"), x, s.qkv, d, hk.PRO_RMSNORM, L["ln1_w"], adapter=ad.get((li, "qkv")))
-                kc, vc = cache[:2]
-                if kv8:  # kv_cache="fp8": the same launch on e4m3 codes + scale bytes, the new rows quantised as they are appended
-                    hk.decode_attn_kv8(s.qkv, kc, vc, cache[2], cache[3], self.cos, self.sin, s.pos, s.o, B, H, hd, max_ctx, scale, nsplit,
-                                       getattr(s, "attn_part", None), getattr(s, "attn_tickets", None), key_mask=kmask, cs=cs)
-                elif hd == 128 and nsplit > 1:  # RoPE + KV append + attention over the cache in one launch, context split over workgroups
-                    hk.decode_attn_split(s.qkv, kc, vc, self.cos, self.sin, s.pos, s.o, B, H, hd, max_ctx, scale, nsplit, s.attn_part,
-                                         s.attn_tickets, key_mask=kmask, cs=cs)
-                elif hd == 128:
-                    hk.decode_attn(s.qkv, kc, vc, self.cos, self.sin, s.pos, s.o, B, H, hd, max_ctx, scale, key_mask=kmask)
-                else:
-                    hk.rope_kv_append(s.qkv, kc, vc, self.cos, self.sin, s.pos, B, H, hd, max_ctx)
-                    hk.attn_fwd(s.qkv[:, :d], kc, vc, s.o, None, s.desc, B, H, hd, 1, 1 << 30, 64, True, scale, key_mask=kmask)
-                lin(*W(L, "o_w"), s.o, x2, d, residual=x, adapter=ad.get((li, "o")))
-                lin(*W(L, "gu_w"), x2, s.gu, d, hk.PRO_RMSNORM, L["ln2_w"], adapter=ad.get((li, "gu")))
-                lin(*W(L, "down_w"), s.gu, x, ff, hk.PRO_SWIGLU, residual=x2, adapter=ad.get((li, "down")))
-            w, sc = (self.p["lm_head8p"], self.p["lm_head8s"]) if fp8 else (self.p["lm_headp"] if packed16 else self.p["lm_head"], None)
-            lin(w, sc, x, s.logits, d, hk.PRO_RMSNORM, self.p["norm_w"], out_f32=True)
-
-        s.enqueue = enqueue
-        s.graph = None
-        return s
-
     def _lora_merged_layers(self):
         """Decoder layers with W + s B A in place of every adapted weight (copies; the base stays untouched) for generate() with un-merged
         adapters.  Cached together with the decode re-tilings / e4m3 copies that `_decode_session` hangs onto the dicts, keyed on the adapter
@@ -1111,13 +818,12 @@ class TextModal:
         cache = getattr(self, "_merged_cache", None)
         if cache is not None and cache[0] == (id(lo), lo.version):
             return cache[1]
-        wname = {"qkv": "qkv_w", "o": "o_w", "gu": "gu_w", "down": "down_w"}
         out = []
         for li, L in enumerate(self.p["layers"]):
             M = {k: L[k] for k in ("ln1_w", "ln2_w", "qkv_w", "o_w", "gu_w", "down_w")}
             for gname in lo.groups:
-                W = L[wname[gname]]
-                M[wname[gname]] = hk.gemm_nt(lo.derived[(li, gname, "Bfull")], lo.derived[(li, gname, "AT")], residual=W, alpha=lo.s)
+                W = L[gname + "_w"]
+                M[gname + "_w"] = hk.gemm_nt(lo.derived[(li, gname, "Bfull")], lo.derived[(li, gname, "AT")], residual=W, alpha=lo.s)
             out.append(M)
         self._merged_cache = ((id(lo), lo.version), out)
         return out
@@ -1141,19 +847,17 @@ class TextModal:
         with un-merged adapters unless `adapters="live"`.
         "mxfp4" - on any base: the decoder linears stream OCP MXFP4 copies (e2m1 codes + one e8m0 scale per 32 k, 0.53 B per weight, made by
         `pack_mx4_decode` from whatever bf16 weights the decoder holds at the first call - merged copies included) against per-row e4m3
-        activations, dequantised and multiplied by the block-scaled MFMA itself (`hk.gemv_mx4`).  Lossy like "fp8" (the weights are rounded to
-        4 bits); lm_head stays bf16, and the prefill stays on the bf16 GEMMs in every mode but "int8".
+        activations on the block-scaled MFMA (`hk.gemv_mx4`).  Lossy like "fp8"; the prefill stays on the bf16 GEMMs in every mode but "int8".
         "int8" - only on the LLM.int8 base (`quantize_base(8, "int8")`, else ValueError): the decoder linears stream the base's own int8 rows
-        and row factors (1 B per weight, re-tiled once by `pack_int8_decode`) in the arithmetic of bitsandbytes' MatMul8bitLt - per linear
-        `hk.int8_decode_prepare` (prologue, outlier columns >= 6.0, per-row int8 codes) and `hk.gemv_int8` (exact int32 product on the int8
-        MFMA + the 16-bit outlier columns) -, and the prefill and the batch > 16 step run `hk.int8_linear`, so the whole call computes what the
-        reference's `generate` computes on a `load_in_8bit` model.  lm_head stays bf16.  With un-merged adapters it needs `adapters="live"`.
+        and row factors (1 B per weight, re-tiled once by `pack_int8_decode`) in the arithmetic of bitsandbytes' MatMul8bitLt (per linear
+        `hk.int8_decode_prepare` + `hk.gemv_int8`), and the prefill and the batch > 16 step run `hk.int8_linear`: the whole call computes what
+        the reference's `generate` computes on a `load_in_8bit` model.  With un-merged adapters it needs `adapters="live"`.  lm_head stays bf16
+        in every format but "fp8".
 
-        `kv_cache`: "bf16" (default) or "fp8" - the K / V caches hold e4m3 codes and one e8m0 scale byte per head row (the kv8 format of
-        csrc/decode_kv8.hip: half the cache memory, half the cache stream of a step and of a beam reorder).  The prefill attends over the exact
-        bf16 K / V of the prompt, so its logits and the first token are those of "bf16"; from the second token on the step reads the rounded
-        cache (`hk.decode_attn_kv8`).  Works with every `weights` / `adapters` / sampler mode, left padding and beams; needs head_dim 128 and
-        batch x num_beams <= 16, else ValueError."""
+        `kv_cache`: "bf16" (default) or "fp8" - e4m3 codes and one e8m0 scale byte per head row (the kv8 format of csrc/decode_kv8.hip: half
+        the cache memory and stream).  The prefill attends over the exact bf16 K / V of the prompt, so its logits and the first token are those
+        of "bf16"; from the second token on the step reads the rounded cache (`hk.decode_attn_kv8`).  Works with every `weights` / `adapters` /
+        sampler mode, left padding and beams; needs head_dim 128 and batch x num_beams <= 16, else ValueError."""
         if adapters not in ("merged", "live"):
             raise ValueError(f"adapters={adapters!r}: expected 'merged' or 'live'")
         nb_ = int(num_beams) if int(num_beams) >= 1 else 1
@@ -1171,8 +875,8 @@ class TextModal:
                   eos_token_id=eos_token_id, return_logits=return_logits, use_graph=use_graph, weights=weights, sampler=sampler, seed=seed,
                   repetition_penalty=repetition_penalty, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
                   return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1), kv_cache=kv_cache)
-        if weights == "int8" and not self.base_int8:
-            raise ValueError('weights="int8" needs the LLM.int8 base: quantize_base(8, "int8") (YAML `bits: 8`)')
+        if generation.int8_gemm(weights) and not self.base_int8:
+            raise ValueError(generation.NO_BASE["int8"][0])
         if self.lora is None:
             return self._generate(input_ids, **kw)
         if adapters == "live":   # nothing is merged or swapped: the bf16 base weights serve prefill, `weights` picks the decode stream, dropout is off
@@ -1197,282 +901,6 @@ class TextModal:
             return self._generate(input_ids, **kw)
         finally:
             self.p["layers"], self.base8, self.base_int8 = base_layers, base8, base_i8
-
-    def _generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p=None,
-                  top_k=None, max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id=None,
-                  return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1,
-                  length_penalty=1.0, early_stopping=False, return_beam_scores=False, num_return_sequences=1, live_lora=False, kv_cache="bf16",
-                  **_kw):
-        """TextModal.generate (text_modal.py:528-627): prefill over the spliced embeddings, then one token at a time with
-        a KV cache; returns only the NEW token ids [B, n_new] (HF generate started from inputs_embeds).  Greedy
-        (do_sample=False, the evaluation scripts' mode) runs entirely in HIP kernels; with do_sample=True the HIP-computed
-        fp32 logits go through HF's temperature / top-k / top-p warpers and one multinomial draw per token.  The
-        single-token step is a captured hipGraph over static buffers (batch <= 16; from batch 2 the weight stream runs on MFMA); without eos / stopping criteria / streamer
-        the host never synchronises inside the loop.
-
-        sampler="device" (with do_sample=True) replaces the torch warpers and `torch.multinomial` by ONE launch of `hk.sample_rows` per token,
-        between the graph replay and `decode_emit`: same distribution as HF, drawn by Philox from (`seed`, step, row) - `seed=None` takes
-        `torch.initial_seed()`, so `torch.manual_seed` still pins a run.  `repetition_penalty != 1` (HF RepetitionPenaltyLogitsProcessor over the
-        tokens generated so far in this call) exists in that kernel only, so it routes every pick through it whatever `sampler` says:
-        mode 0 when sampling, mode 1 (first maximum of the penalised logits) when greedy.  "One launch and nothing else" holds without an
-        EOS: with `eos_token_id` set the pad replacement of finished rows (`torch.where` + `copy_`) and the host's check still run between the
-        pick and `decode_emit`, as they do for greedy; the kernel has then already set the drawn token's bit in the seen bitmap of a finished
-        row, which nothing reads any more."""
-        if sampler not in ("torch", "device"):
-            raise ValueError(f"sampler={sampler!r}: expected 'torch' or 'device'")
-        if int(num_beams) != 1:
-            return self._generate_beam(input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer,
-                                       eos_token_id, return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty,
-                                       early_stopping, return_beam_scores, num_return_sequences, live_lora, kv_cache)
-        self._check_kv_cache(kv_cache, int(input_ids.shape[0]))
-        pen = float(repetition_penalty)
-        device_pick = (sampler == "device" and do_sample) or pen != 1.0
-        if streamer is not None and getattr(streamer, "skip_prompt", False):
-            streamer.put(input_ids.cpu())  # transformers.TextStreamer protocol: the first put() is the prompt, which skip_prompt drops
-        embeds, _, mask, _ = self.prepare_inputs_for_multimodal(input_ids, attention_mask, None, image_embedding)
-        B, S0, d = embeds.shape
-        max_ctx = S0 + max_new_tokens
-        if max_ctx > self.cos.shape[0]:
-            raise ValueError(f"prompt ({S0}) + max_new_tokens ({max_new_tokens}) exceeds the {self.cos.shape[0]} positions of the RoPE table")
-        dev = self.device
-        kmask = None
-        if mask is not None and not bool(mask.bool().all()):
-            # batched evaluation with LEFT-padded prompts (DataCollatorForVGSupervisedDataset -> main_vqa.py:205-214): HF keeps
-            # position_ids = arange (CustomLlamaForCausalLM.prepare_inputs_for_generation passes none) and hides the keys whose
-            # (spliced) attention_mask is 0; every generated position is visible.
-            kmask = torch.ones((B, max_ctx), device=dev, dtype=torch.uint8)
-            kmask[:, :S0] = mask.to(device=dev, dtype=torch.uint8)
-        caches = self._alloc_kv(B * max_ctx, kv_cache)
-
-        lora = self.lora if live_lora else None   # adapters="live": the store the session and the GEMM steps read
-        w8i = weights == "int8"                   # prefill and the batch > 16 step run the LLM.int8 products too: the whole call is in that arithmetic
-        s, seen, step_dev = None, None, None
-        if device_pick:
-            seed = int(torch.initial_seed() if seed is None else seed)
-            if pen != 1.0:  # bitmap of the tokens generated so far in this call (HF started from inputs_embeds: the prompt is not in it)
-                seen = torch.zeros((B, (self.vocab + 31) // 32), device=dev, dtype=torch.int32)
-            if B <= 16:  # the draw's step counter is the session's count of emitted tokens, on the device
-                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora, kv_cache)
-                s.state[0], s.state[1] = S0, 0
-                step_dev = s.state[1:2]
-
-        def pick_device(logits, out=None, step_host=0):
-            return hk.sample_rows(logits, out, mode=0 if do_sample else 1, temperature=temperature, top_k=top_k, top_p=top_p,
-                                  repetition_penalty=pen, seen=seen, seed=seed, step_dev=step_dev, step_host=step_host)
-
-        def pick(logits):
-            if device_pick:
-                return pick_device(logits, None if s is None else s.next_ids, 0 if s is not None else n_done)
-            if not do_sample:
-                return hk.argmax_rows(logits)
-            return torch.multinomial(torch.softmax(warp_logits(logits, temperature, top_k, top_p), -1), 1).squeeze(1)
-
-        # ---- prefill (GEMM path) -> logits of the last prompt position -> first new token
-        # kv_cache="fp8": the prompt's attention reads K / V out of the qkv buffer itself, where sequence b starts at row b * S0
-        desc = hk.make_desc([(b * S0, S0, b * (S0 if kv_cache == "fp8" else max_ctx), S0, S0, 0) for b in range(B)], dev)
-        x = embeds.reshape(B * S0, d)
-        for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
-            x = self._layer_step(L, x, B, S0, 0, cache, desc, max_ctx, kmask, li=li if lora is not None or w8i else None, int8=w8i)
-        hn = hk.rmsnorm_fwd(x.view(B, S0, d)[:, -1].contiguous(), self.p["norm_w"], self.eps)
-        logits = hk.gemm_nt(hn, self.p["lm_head"], out_f32=True)  # [B, V] fp32 (HF: logits.float())
-        all_logits = [logits.clone()] if return_logits else []
-        n_done = 0
-        nxt = pick(logits)
-
-        host_checks = eos_token_id is not None or stopping_criteria is not None or streamer is not None
-        finished = torch.zeros(B, dtype=torch.bool, device=dev)
-
-        def host_step(ids_so_far, lg):  # -> stop?
-            nonlocal finished
-            if streamer is not None:
-                streamer.put(ids_so_far[:, -1].cpu())
-            if eos_token_id is not None:
-                finished |= ids_so_far[:, -1] == eos_token_id
-                if bool(finished.all()):
-                    return True
-            return stopping_criteria is not None and any(c(ids_so_far, lg) for c in stopping_criteria)
-
-        n_done = 1
-        if B <= 16:
-            if s is None:
-                s = self._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora, kv_cache)
-                s.state[0], s.state[1] = S0, 0
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                if nxt is not s.next_ids:
-                    s.next_ids.copy_(nxt)
-                hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, B, max_new_tokens)
-                stop = host_checks and host_step(s.out_ids[:, :1], logits)
-                while not stop and n_done < max_new_tokens:
-                    if use_graph and s.graph is None and n_done >= 2:  # one eager step first (lazy kernel attributes), then capture
-                        g = hk.HipGraph()
-                        g.begin()
-                        s.enqueue()
-                        g.end()
-                        s.graph = g
-                        s.graph.launch()
-                    elif s.graph is not None:
-                        s.graph.launch()
-                    else:
-                        s.enqueue()
-                    if return_logits:
-                        all_logits.append(s.logits.clone())
-                    if device_pick:
-                        pick_device(s.logits, s.next_ids)
-                    elif do_sample:
-                        s.next_ids.copy_(pick(s.logits))
-                    else:
-                        hk.argmax_rows(s.logits, out=s.next_ids)
-                    if eos_token_id is not None:
-                        s.next_ids.copy_(torch.where(finished, torch.full_like(s.next_ids, self.tokenizer.pad_token_id), s.next_ids))
-                    hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, B, max_new_tokens)
-                    n_done += 1
-                    if host_checks:
-                        stop = host_step(s.out_ids[:, :n_done], s.logits)
-            torch.cuda.current_stream().wait_stream(side)
-            ids = s.out_ids[:, :n_done].clone()
-        else:
-            out_ids = [nxt]
-            ctx = S0
-            stop = host_checks and host_step(torch.stack(out_ids, 1), logits)
-            while not stop and n_done < max_new_tokens:
-                x = hk.gather_rows(self.p["embed"], out_ids[-1].clamp(0, self.vocab - 1).to(torch.int32))
-                desc = hk.make_desc([(b, 1, b * max_ctx, ctx + 1, ctx + 1, ctx) for b in range(B)], dev)
-                for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
-                    x = self._layer_step(L, x, B, 1, ctx, cache, desc, max_ctx, kmask, li=li if lora is not None or w8i else None, int8=w8i)
-                logits = hk.gemm_nt(hk.rmsnorm_fwd(x, self.p["norm_w"], self.eps), self.p["lm_head"], out_f32=True)
-                if return_logits:
-                    all_logits.append(logits.clone())
-                nxt = pick(logits)
-                if eos_token_id is not None:
-                    nxt = torch.where(finished, torch.full_like(nxt, self.tokenizer.pad_token_id), nxt)
-                out_ids.append(nxt)
-                ctx += 1
-                n_done += 1
-                if host_checks:
-                    stop = host_step(torch.stack(out_ids, 1), logits)
-            ids = torch.stack(out_ids, 1)
-        if streamer is not None:
-            streamer.end()
-        return (ids, torch.stack(all_logits, 1)) if return_logits else ids
-
-    def _generate_beam(self, input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer, eos_token_id,
-                       return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty, early_stopping, return_beam_scores,
-                       num_return_sequences, live_lora=False, kv_cache="bf16"):
-        """Deterministic beam search, HF `generate(num_beams=nb, do_sample=False)` (generation/utils.py _beam_search; the web UI's
-        answer_prepare kwargs): the prompt is prefilled ONCE per batch row into cache row b * nb and replicated to the row's other beams by
-        `hk.kv_beam_reorder`; every further token is one linear single-stream graph of [model step over B * nb rows, beam_topk_rows, beam_step,
-        kv_beam_reorder, decode_emit] (csrc/beam.hip).  All bookkeeping - running scores, parents, token histories, the finished set, the
-        early-stop heuristic and the batch-wide `done` word - lives on the device; the host reads `done` every fourth token when an EOS is set
-        (once done, the kernels change nothing, so the extra steps do not show) and never without one.  -> ids [B, L] of each row's best
-        hypothesis, pad_token_id past its end (, logits [B * nb, n, V] of the running beams)(, scores [B])."""
-        nb = int(num_beams)
-        if nb < 1:
-            raise ValueError(f"num_beams={num_beams!r}: must be >= 1")
-        if do_sample:
-            raise ValueError("do_sample=True with num_beams > 1 (beam-multinomial sampling) is not implemented")
-        if streamer is not None:
-            raise ValueError("streamer is not supported with num_beams > 1 (HF: beam search has no token stream)")
-        if stopping_criteria is not None:
-            raise ValueError("stopping_criteria is not supported with num_beams > 1: stopping is eos_token_id / max_new_tokens, on the device")
-        if int(num_return_sequences) != 1:
-            raise ValueError(f"num_return_sequences={num_return_sequences!r}: only the best hypothesis of each row is returned")
-        if early_stopping not in (False, True):
-            raise ValueError(f"early_stopping={early_stopping!r}: False or True ('never' is not implemented)")
-        self._check_kv_cache(kv_cache, int(input_ids.shape[0]) * nb, nb)
-        embeds, _, mask, _ = self.prepare_inputs_for_multimodal(input_ids, attention_mask, None, image_embedding)
-        B, S0, d = embeds.shape
-        R = B * nb
-        if nb > 8 or R > 16:
-            raise ValueError(f"num_beams={nb} with batch {B}: batch * num_beams must be <= 16 (and num_beams <= 8)")
-        V, dev, pen = self.vocab, self.device, float(repetition_penalty)
-        max_ctx = S0 + max_new_tokens
-        if max_ctx > self.cos.shape[0]:
-            raise ValueError(f"prompt ({S0}) + max_new_tokens ({max_new_tokens}) exceeds the {self.cos.shape[0]} positions of the RoPE table")
-        kmask = kmask_r = None
-        if mask is not None and not bool(mask.bool().all()):   # left-padded prompts, as in _generate; every beam hides its row's padding
-            kmask = torch.ones((B, max_ctx), device=dev, dtype=torch.uint8)
-            kmask[:, :S0] = mask.to(device=dev, dtype=torch.uint8)
-            kmask_r = kmask.repeat_interleave(nb, 0).contiguous()
-        kv8 = kv_cache == "fp8"
-        caches = self._alloc_kv(R * max_ctx, kv_cache)
-        lora = self.lora if live_lora else None
-        w8i = weights == "int8"
-        s = self._decode_session(R, max_ctx, caches, max_new_tokens, weights, kmask_r, lora, kv_cache)
-        s.state[0], s.state[1] = S0, 0
-        st = hk.BeamState(B, nb, V, max_new_tokens, length_penalty, dev)
-        # kv_beam_reorder is a byte copy in 16-byte chunks whose `d` counts 2-byte units: the bf16 caches with d, the kv8 code caches with d / 2
-        # and the scale arrays with H / 2 - codes and scales move together, in two launches
-        if kv8:
-            tables = [(hk.kv_cache_table([c[:2] for c in caches], dev), d // 2), (hk.kv_cache_table([c[2:] for c in caches], dev), self.heads // 2)]
-        else:
-            tables = [(hk.kv_cache_table(caches, dev), d)]
-
-        # ---- prefill: sequence b into cache row b * nb (a cache "row" of nb * max_ctx positions), logits of the last prompt position
-        desc = hk.make_desc([(b * S0, S0, b * (S0 if kv8 else nb * max_ctx), S0, S0, 0) for b in range(B)], dev)
-        x = embeds.reshape(B * S0, d)
-        for li, (L, cache) in enumerate(zip(self.p["layers"], caches)):
-            x = self._layer_step(L, x, B, S0, 0, cache, desc, nb * max_ctx, kmask, li=li if lora is not None or w8i else None, int8=w8i)
-        hn = hk.rmsnorm_fwd(x.view(B, S0, d)[:, -1].contiguous(), self.p["norm_w"], self.eps)
-        logits = hk.gemm_nt(hn, self.p["lm_head"], out_f32=True).repeat_interleave(nb, 0).contiguous()   # the row's beams all start from it
-        all_logits = [logits] if return_logits else []
-
-        def beam_tail(lg, t0, t1):
-            hk.beam_topk_rows(lg, st, pen)
-            hk.beam_step(st, s.next_ids, eos_token_id, early_stopping)
-            for table, units in tables:
-                hk.kv_beam_reorder(table, B, nb, max_ctx, units, st.parent, t0, t1, S0 if t0 == 0 else max_new_tokens, done=st.bstate[1:2])
-            hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, R, max_new_tokens)
-
-        def step():
-            s.enqueue()
-            beam_tail(s.logits, S0, s.state[0:1])
-
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            beam_tail(logits, 0, S0)          # parents are all 0: replicates the prompt's cache to every beam of the row
-            n_done = 1
-            while n_done < max_new_tokens:
-                if use_graph and s.graph is None and n_done >= 2:  # one eager step first (lazy kernel attributes), then capture
-                    g = hk.HipGraph()
-                    g.begin()
-                    step()
-                    g.end()
-                    s.graph = g
-                    s.graph.launch()
-                elif s.graph is not None:
-                    s.graph.launch()
-                else:
-                    step()
-                if return_logits:
-                    all_logits.append(s.logits.clone())
-                n_done += 1
-                if eos_token_id is not None and n_done % 4 == 0 and int(st.bstate[1].item()):
-                    break
-        torch.cuda.current_stream().wait_stream(side)
-        # ---- the result of each row: its best finished hypothesis, else its best running beam (tiny host-side epilogue, once per call)
-        n = int(st.bstate[0].item())
-        fin_score, fin_len, fin_slot = st.fin_score.view(B, nb).cpu(), st.fin_len.view(B, nb).cpu(), st.fin_slot.view(B, nb).cpu()
-        fin_seq, hist, run = st.fin_seq.view(B, nb, -1).cpu(), st.hist[n & 1].view(B, nb, -1).cpu(), st.run_score.view(B, nb).cpu()
-        rows, scores = [], []
-        for b in range(B):
-            if int(fin_len[b, 0]) > 0:
-                rows.append(fin_seq[b, int(fin_slot[b, 0]), :int(fin_len[b, 0])])
-                scores.append(float(fin_score[b, 0]))
-            else:
-                rows.append(hist[b, 0, :n])
-                scores.append(float(run[b, 0]))
-        ids = torch.full((B, max(len(r) for r in rows)), int(self.tokenizer.pad_token_id), dtype=torch.int64)
-        for b, r in enumerate(rows):
-            ids[b, :len(r)] = r
-        out = (ids.to(dev),)
-        if return_logits:
-            out += (torch.stack(all_logits[:n], 1),)
-        if return_beam_scores:
-            out += (torch.tensor(scores, dtype=torch.float32, device=dev),)
-        return out if len(out) > 1 else out[0]
 
     # ------------------------------------------------------------------ backward (activation gradients only)
     def backward(self, loss_scale: float = 1.0, need_input_grad: bool = True, on_layer_ready=None):
