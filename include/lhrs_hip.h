@@ -478,7 +478,7 @@ int lhrs_decode_attn(const void* qkv, long ld, void* kcache, void* vcache, const
 int lhrs_decode_attn_split(const void* qkv, long ld, void* kcache, void* vcache, const float* cos_t, const float* sin_t,
                            const int* pos, const unsigned char* key_mask, long ld_mask, void* out, long ldo, int B, int H, int D,
                            int max_ctx, float scale, int nsplit, float* part, int* tickets, const float* cs, void* stream);
-/* ---- the 8-bit KV cache "kv8" (csrc/decode_kv8.hip; TextModal.generate(kv_cache="fp8")): one cache position of one head = 128 values
+/* ---- the 8-bit KV cache "kv8" (csrc/decode_attn.hip; TextModal.generate(kv_cache="fp8")): one cache position of one head = 128 values
  * (keys after RoPE, already rounded to bf16) -> 128 OCP e4m3fn codes + one e8m0 scale byte.  m = max|v| of the 128: m == 0 -> byte 127 and
  * +0 codes; else e = floor(log2 m) - 8, raised by one if m > 448 * 2^e, byte = clamp(e + 127, 0, 254), code = RNE_e4m3(v / 2^e): nothing
  * saturates, no code is a NaN.  Per layer and per K / V, position-major like the bf16 caches: codes uint8 [rows * max_ctx][H * 128], scales

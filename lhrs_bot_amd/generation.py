@@ -109,7 +109,7 @@ DECODE_SUFFIXES = tuple(f.operand for f in FORMATS.values())   # the `<weight na
 
 
 def check_kv_cache(m, kv_cache, rows, num_beams=1):
-    """generate(kv_cache=...), "fp8" = the kv8 format of csrc/decode_kv8.hip: what it cannot serve raises here, before anything is allocated"""
+    """generate(kv_cache=...), "fp8" = the kv8 format of csrc/decode_attn.hip: what it cannot serve raises here, before anything is allocated"""
     if kv_cache not in ("bf16", "fp8"):
         raise ValueError(f"kv_cache={kv_cache!r}: expected 'bf16' or 'fp8'")
     if kv_cache == "bf16":

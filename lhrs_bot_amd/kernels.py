@@ -912,11 +912,19 @@ def rope_kv_append(qkv, kc, vc, cos_t, sin_t, pos, B, H, D, max_ctx):
                                         pos.data_ptr(), B, H, D, max_ctx, _stream()), "rope_kv_append")
 
 
+def _key_mask_args(key_mask):
+    """pointer and row stride of the HF attention_mask bytes the decode attention entry points take (NULL, 0 without a mask)"""
+    return _p(key_mask), key_mask.stride(0) if key_mask is not None else 0
+
+
+def _check_split_buffers(part, tickets, B, H, nsplit):
+    assert part.dtype == torch.float32 and part.numel() >= B * H * nsplit * 132 and tickets.dtype == torch.int32 and tickets.numel() >= B * H
+
+
 def decode_attn(qkv, kc, vc, cos_t, sin_t, pos, out, B, H, D, max_ctx, scale, key_mask=None):
     """RoPE(new q, k) + KV append + attention over the cache for one new token per sequence, one launch (lhrs_decode_attn)."""
     st = _L().lhrs_decode_attn(qkv.data_ptr(), qkv.stride(0), kc.data_ptr(), vc.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(), pos.data_ptr(),
-                               _p(key_mask), key_mask.stride(0) if key_mask is not None else 0, out.data_ptr(), out.stride(0), B, H, D,
-                               max_ctx, float(scale), _stream())
+                               *_key_mask_args(key_mask), out.data_ptr(), out.stride(0), B, H, D, max_ctx, float(scale), _stream())
     _lib.check(st, "decode_attn")
     return out
 
@@ -924,10 +932,10 @@ def decode_attn(qkv, kc, vc, cos_t, sin_t, pos, out, B, H, D, max_ctx, scale, ke
 def decode_attn_split(qkv, kc, vc, cos_t, sin_t, pos, out, B, H, D, max_ctx, scale, nsplit, part, tickets, key_mask=None, cs=None):
     """decode_attn with the context split over `nsplit` workgroups per head (lhrs_decode_attn_split); part fp32 [B, H, nsplit, 132],
     tickets int32 [B, H] (zero before the first call)."""
-    assert part.dtype == torch.float32 and part.numel() >= B * H * nsplit * 132 and tickets.dtype == torch.int32 and tickets.numel() >= B * H
+    _check_split_buffers(part, tickets, B, H, nsplit)
     st = _L().lhrs_decode_attn_split(qkv.data_ptr(), qkv.stride(0), kc.data_ptr(), vc.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(),
-                                     pos.data_ptr(), _p(key_mask), key_mask.stride(0) if key_mask is not None else 0, out.data_ptr(),
-                                     out.stride(0), B, H, D, max_ctx, float(scale), int(nsplit), part.data_ptr(), tickets.data_ptr(), _p(cs), _stream())
+                                     pos.data_ptr(), *_key_mask_args(key_mask), out.data_ptr(), out.stride(0), B, H, D, max_ctx, float(scale),
+                                     int(nsplit), part.data_ptr(), tickets.data_ptr(), _p(cs), _stream())
     _lib.check(st, "decode_attn_split")
     return out
 
@@ -953,11 +961,10 @@ def decode_attn_kv8(qkv, kc8, vc8, ks, vs, cos_t, sin_t, pos, out, B, H, D, max_
         _req(t, torch.uint8, name)
         assert t.is_contiguous() and t.shape[0] >= B * max_ctx and t.shape[1] == (H * D if t is kc8 or t is vc8 else H), name
     if nsplit > 1:
-        assert part.dtype == torch.float32 and part.numel() >= B * H * nsplit * 132 and tickets.dtype == torch.int32 and tickets.numel() >= B * H
+        _check_split_buffers(part, tickets, B, H, nsplit)
     st = _L().lhrs_decode_attn_kv8(qkv.data_ptr(), qkv.stride(0), kc8.data_ptr(), vc8.data_ptr(), ks.data_ptr(), vs.data_ptr(), cos_t.data_ptr(),
-                                   sin_t.data_ptr(), pos.data_ptr(), _p(key_mask), key_mask.stride(0) if key_mask is not None else 0,
-                                   out.data_ptr(), out.stride(0), B, H, D, max_ctx, float(scale), int(nsplit), _p(part), _p(tickets), _p(cs),
-                                   _stream())
+                                   sin_t.data_ptr(), pos.data_ptr(), *_key_mask_args(key_mask), out.data_ptr(), out.stride(0), B, H, D, max_ctx,
+                                   float(scale), int(nsplit), _p(part), _p(tickets), _p(cs), _stream())
     _lib.check(st, "decode_attn_kv8")
     return out
 

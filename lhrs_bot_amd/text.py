@@ -854,7 +854,7 @@ class TextModal:
         the reference's `generate` computes on a `load_in_8bit` model.  With un-merged adapters it needs `adapters="live"`.  lm_head stays bf16
         in every format but "fp8".
 
-        `kv_cache`: "bf16" (default) or "fp8" - e4m3 codes and one e8m0 scale byte per head row (the kv8 format of csrc/decode_kv8.hip: half
+        `kv_cache`: "bf16" (default) or "fp8" - e4m3 codes and one e8m0 scale byte per head row (the kv8 format of csrc/decode_attn.hip: half
         the cache memory and stream).  The prefill attends over the exact bf16 K / V of the prompt, so its logits and the first token are those
         of "bf16"; from the second token on the step reads the rounded cache (`hk.decode_attn_kv8`).  Works with every `weights` / `adapters` /
         sampler mode, left padding and beams; needs head_dim 128 and batch x num_beams <= 16, else ValueError."""

@@ -1,5 +1,6 @@
-"""The bf16 decode attention (csrc/decode.hip behind hk.decode_attn / hk.decode_attn_split, and the composed route hk.rope_kv_append +
-hk.attn_fwd of a model whose head_dim is not 128), the exported hk.kv_append and the step bookkeeping (hk.decode_advance / hk.decode_emit),
+"""The bf16 decode attention (csrc/decode_attn.hip behind hk.decode_attn / hk.decode_attn_split, and the composed route hk.rope_kv_append +
+hk.attn_fwd of a model whose head_dim is not 128), the exported hk.kv_append and the step bookkeeping (hk.decode_advance / hk.decode_emit;
+csrc/decode.hip),
 restated for tests/test_decode_attn_cases_cpu.py and tests/test_decode_attn_gpu.py.  Shares no code with the HIP source.
 
 Inputs.  B = 3 sequences, each at its own position pos[b]; H = 2 heads of D = 128 (the composed route also H = 4, D = 64).  qkv is bf16

@@ -1,4 +1,4 @@
-"""The 8-bit KV cache "kv8" (csrc/decode_kv8.hip behind hk.kv8_quant_rows / hk.decode_attn_kv8, generate(kv_cache="fp8")), restated for
+"""The 8-bit KV cache "kv8" (csrc/decode_attn.hip behind hk.kv8_quant_rows / hk.decode_attn_kv8, generate(kv_cache="fp8")), restated for
 tests/test_kv8_cases_cpu.py and tests/test_kv8_gpu.py.  Shares no code with the HIP source.
 
 Format.  One cache position of one head is 128 values (keys after RoPE, already rounded to bf16).  It becomes 128 OCP e4m3fn codes and one

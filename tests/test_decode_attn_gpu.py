@@ -1,4 +1,4 @@
-"""The bf16 decode attention of csrc/decode.hip on an MI355X against the float64 restatement of tests/decode_attn_cases.py:
+"""The bf16 decode attention of csrc/decode_attn.hip on an MI355X against the float64 restatement of tests/decode_attn_cases.py:
 hk.decode_attn and hk.decode_attn_split on every case of its table, the composed route hk.rope_kv_append + hk.attn_fwd at head_dim 128 and
 64, the exported hk.kv_append, the step bookkeeping hk.decode_advance / hk.decode_emit against integer models, and which of them generate()
 reaches.

@@ -1,4 +1,4 @@
-"""Decode from an e4m3 KV cache (csrc/decode_kv8.hip behind hk.kv8_quant_rows / hk.decode_attn_kv8, generate(kv_cache="fp8")) on an MI355X,
+"""Decode from an e4m3 KV cache (csrc/decode_attn.hip behind hk.kv8_quant_rows / hk.decode_attn_kv8, generate(kv_cache="fp8")) on an MI355X,
 against the restatement of tests/kv8_cases.py.
 
 Format: codes and scale bytes byte for byte, read from a strided qkv buffer with a NaN surround, written at a non-zero cache row of a
