@@ -69,6 +69,9 @@ def parse_option(args=None):
     p.add_argument("--kv-cache", default="bf16", choices=["bf16", "fp8"],
                    help="KV cache of the decode step: bf16, or fp8 = e4m3 codes with one e8m0 scale byte per head row (half the cache memory and "
                         "half the cache stream; the prompt itself is attended in bf16, so the first token is the bf16 one); batch x beams <= 16")
+    p.add_argument("--prefix-cache", action="store_true",
+                   help="keep the KV cache of the conversation across turns (one PrefixCache of the chosen --kv-cache): a turn encodes no image "
+                        "again and prefills only what is new behind the common prefix of its prompt and the cache; not with --num-beams > 1")
     p.add_argument("--length-penalty", type=float, default=1.0, help="HF length_penalty of the beam search: hypotheses score sum(log p) / length ** penalty")
     cfg = ConfigDict(p.parse_args(wandb=True, args=args))
     opts = cfg.get("opts") or []
@@ -106,6 +109,8 @@ def load_image(path):
 def main(config):
     if config.accelerator != "gpu" or not torch.cuda.is_available():
         raise RuntimeError("cli_qa.py drives the HIP engine: it needs --accelerator gpu and a visible MI355X (there is no CPU path)")
+    if config.get("prefix_cache") and int(config.num_beams) > 1:
+        raise ValueError("--prefix-cache with --num-beams > 1: beam search starts every turn from an empty cache")
     device = torch.device("cuda", 0)
     torch.manual_seed(int(config.seed))
     # build_model loads the frozen towers + tokenizer from config.text.path / config.rgb_vision.vit_name (random-init with a warning when
@@ -127,6 +132,7 @@ def main(config):
     weights = config.get("decode_weights") or ("fp8" if bits == 8 else "bf16")
     adapters = str(config.get("adapters") or "merged")
     kv_cache = str(config.get("kv_cache") or "bf16")
+    turn_kw = {"prefix_cache": model.new_prefix_cache(kv_cache)} if config.get("prefix_cache") else {}
     if weights == "4bit":
         if bits != 4:
             raise ValueError("--decode-weights 4bit requires `bits: 4` in the YAML (or --opts bits 4)")
@@ -199,7 +205,7 @@ def main(config):
                 output_ids = model.generate(input_ids, images=image_tensor, do_sample=True, max_new_tokens=int(config.max_new_tokens), temperature=0.4,
                                             streamer=_Streamer(tokenizer), use_cache=True, stopping_criteria=[stopping_criteria], weights=weights,
                                             sampler=config.sampler, repetition_penalty=float(config.repetition_penalty), seed=int(config.seed),
-                                            adapters=adapters, kv_cache=kv_cache)
+                                            adapters=adapters, kv_cache=kv_cache, **turn_kw)
         outputs = tokenizer.decode(output_ids[0]).strip().split("<s>")[-1].strip()
         conv.messages[-1][-1] = outputs
         if config.debug:

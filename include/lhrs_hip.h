@@ -486,6 +486,10 @@ int lhrs_decode_attn_split(const void* qkv, long ld, void* kcache, void* vcache,
  * kv8_quant_rows: src = bf16 rows [n][H * 128], row stride ld elements (ld % 8 == 0; the K or V column block of a qkv buffer in place) ->
  * codes and scale bytes of the cache rows row0 .. row0 + n - 1. */
 int lhrs_kv8_quant_rows(const void* src, long ld, void* codes, void* scales, long row0, int n, int H, void* stream);
+/* kv8_dequant_rows, the inverse: the cache rows row0 .. row0 + n - 1 -> dst = bf16 rows [n][H * 128], row pitch ld elements (ld % 8 == 0,
+ * >= H * 128; columns past H * 128 are not written).  value = e4m3(code) * 2^(byte - 127) in fp32, rounded to bf16 RNE: exact wherever the
+ * product is a normal fp32 number that bf16 can hold (an e4m3 value has at most 4 significant bits). */
+int lhrs_kv8_dequant_rows(const void* codes, const void* scales, long row0, int n, int H, void* dst, long ld, void* stream);
 /* lhrs_decode_attn_split on the kv8 caches, nsplit 1..16 (1: no exchange; part / tickets may then be NULL): RoPE of the new q / k row,
  * quantisation of the new K and V head rows, their append (codes and scale byte) at pos[b] and attention over keys 0..pos[b] in ONE launch.
  * The new token attends to the dequantised row it has just written, so the output is a function of the cache bytes alone; rows past the

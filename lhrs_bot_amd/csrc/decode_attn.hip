@@ -3,7 +3,7 @@
 //   lhrs_decode_attn       : bf16 cache, one workgroup per (sequence, head)            <CacheBf16, 8, 16, false>
 //   lhrs_decode_attn_split : bf16 cache, the context split over nsplit workgroups      <CacheBf16, 4, 8, true>
 //   lhrs_decode_attn_kv8   : the same split on the 8-bit cache, generate(kv_cache="fp8") <CacheE4m3, 4, 4, true>
-// and kv8_quant_rows writes the prefill's rows of that cache.
+// and kv8_quant_rows writes the prefill's rows of that cache; kv8_dequant_rows reads rows back as bf16 for a prefill behind cached positions.
 //
 // The 8-bit cache ("kv8").  One cache position of one head - 128 values, keys after RoPE and already rounded to bf16 - is 128 OCP e4m3fn
 // codes and one e8m0 scale byte.  With m = max|v| of the group: m == 0 gives byte 127 and +0 codes; else e = floor(log2 m) - 8, raised by
@@ -97,6 +97,32 @@ __global__ __launch_bounds__(256) void kv8_quant_rows_kernel(const bf16_t* __res
   const uint4 c = k8_quant16(v, byte);
   *reinterpret_cast<uint4*>(codes + (row0 + r) * ((long)H * K8_D) + h * K8_D + l8 * 16) = c;
   if (l8 == 0) scales[(row0 + r) * H + h] = (unsigned char)byte;
+}
+
+// The inverse, for a multi-row prefill behind cached positions (generate(prefix_cache=...)): cache rows row0 .. row0 + n - 1 -> bf16 rows
+// of dst (row pitch ld elements).  value = e4m3(code) * 2^(byte - 127) in fp32, rounded to bf16 RNE.  An e4m3 value has at most 4
+// significant bits and the scale is a power of two, so the product is exact in fp32 and the bf16 is exact too wherever the product is a
+// normal fp32 number that bf16 can hold (below 2^-126 the bf16 subnormals keep fewer bits: the RNE then rounds).  One 8-lane group per
+// (row, head): one 16-B code load and the scale byte per lane, two 16-B stores per lane.
+__global__ __launch_bounds__(256) void kv8_dequant_rows_kernel(const unsigned char* __restrict__ codes, const unsigned char* __restrict__ scales,
+                                                               long row0, int n, int H, bf16_t* __restrict__ dst, long ld) {
+  const long g = (long)blockIdx.x * 32 + (threadIdx.x >> 3);   // (row, head) pair
+  if (g >= (long)n * H) return;
+  const int l8 = threadIdx.x & 7;
+  const long r = g / H;
+  const int h = (int)(g - r * H);
+  const uint4 c = *reinterpret_cast<const uint4*>(codes + (row0 + r) * ((long)H * K8_D) + h * K8_D + l8 * 16);
+  const float sc = k8_pow2((int)scales[(row0 + r) * H + h] - 127);
+  float v[16];
+  k8_dequant16(c, v);
+  bf16_t* out = dst + r * ld + h * K8_D + l8 * 16;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    float t[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) t[e] = v[8 * j + e] * sc;
+    *reinterpret_cast<uint4*>(out + 8 * j) = pack8(t);
+  }
 }
 
 // ---- the two cache formats.  A lane owns 16 bytes of a cached head row: LPG lanes hold the row, EPL = 128 / LPG values each.  `at` is the
@@ -417,6 +443,19 @@ extern "C" int lhrs_kv8_quant_rows(const void* src, long ld, void* codes, void* 
   hipLaunchKernelGGL(kv8_quant_rows_kernel, dim3(cdiv((long)n * H, 32)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, ld,
                      (unsigned char*)codes, (unsigned char*)scales, row0, n, H);
   LHRS_CHECK_LAUNCH("kv8_quant_rows");
+  return 0;
+}
+
+// codes [.., H * 128] and scales [.., H] of the cache rows row0 .. row0 + n - 1 -> dst: bf16 rows [n][H * 128] with a row pitch of ld
+// elements (ld % 8 == 0, 16-byte aligned)
+extern "C" int lhrs_kv8_dequant_rows(const void* codes, const void* scales, long row0, int n, int H, void* dst, long ld, void* stream) {
+  LHRS_REQUIRE(n >= 1 && H >= 1 && row0 >= 0 && ld >= (long)H * K8_D && ld % 8 == 0, "kv8_dequant_rows: n=%d H=%d row0=%ld ld=%ld (ld %% 8 == 0, >= H * 128)",
+               n, H, row0, ld);
+  LHRS_REQUIRE(dst != nullptr && codes != nullptr && scales != nullptr && (uintptr_t)dst % 16 == 0 && (uintptr_t)codes % 16 == 0,
+               "kv8_dequant_rows: codes=%p scales=%p dst=%p (16-byte aligned)", codes, scales, dst);
+  hipLaunchKernelGGL(kv8_dequant_rows_kernel, dim3(cdiv((long)n * H, 32)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)codes,
+                     (const unsigned char*)scales, row0, n, H, (bf16_t*)dst, ld);
+  LHRS_CHECK_LAUNCH("kv8_dequant_rows");
   return 0;
 }
 

@@ -1,5 +1,6 @@
 """Single-token decoding and generation for `TextModal` (text.py binds the functions below under their `TextModal` names): FORMATS, the one
-table of what `generate(weights=...)` can stream; DecodeSession, the static buffers and launch list of one single-token step; the token loops."""
+table of what `generate(weights=...)` can stream; PrefixCache, the KV cache of a conversation kept between calls; DecodeSession, the static
+buffers and launch list of one single-token step; the token loops."""
 import dataclasses
 import math
 import os
@@ -133,11 +134,103 @@ def alloc_kv(m, rows, kv_cache):
     return [(t(m.d, torch.bfloat16), t(m.d, torch.bfloat16)) for _ in m.p["layers"]]
 
 
+# ------------------------------------------------------------------------------------------------- the cache of a conversation
+IMAGE_PLACEHOLDER = -200   # IMAGE_TOKEN_INDEX of text.py (which imports this module)
+
+
+def match_prefix(cached_ids, new_ids, NI, image_same):
+    """How much of a cached sequence a new prompt can reuse -> (tokens, positions).  Both are Python lists of ids in placeholder form: the
+    <image> placeholder (-200) is one entry and stands for NI cache positions.  The answer is the longest common prefix, with two rules:
+    the cut never falls inside the image block - the placeholder is reused whole, and only if `image_same` (the cached block came from the
+    image embedding of the new call) - and at least one position is left to prefill (its logits pick the first token): a new prompt that
+    is cached entirely is reused up to its last entry, which for a trailing placeholder is the whole block."""
+    tokens = positions = 0
+    for a, b in zip(cached_ids, new_ids):
+        if a != b or (a == IMAGE_PLACEHOLDER and not image_same):
+            break
+        tokens, positions = tokens + 1, positions + (NI if a == IMAGE_PLACEHOLDER else 1)
+    if tokens == len(new_ids) and tokens > 0:
+        tokens, positions = tokens - 1, positions - (NI if new_ids[-1] == IMAGE_PLACEHOLDER else 1)
+    return tokens, positions
+
+
+class PrefixCache:
+    """The KV cache of ONE conversation (batch 1) of one model, kept between `generate(prefix_cache=...)` calls: from `new_prefix_cache` of
+    `TextModal` / `UniBind`.  `caches`: `alloc_kv(max_positions, kv_cache)`, made at the first call (None before); `ids`: what the first
+    `length` positions hold, in placeholder form (Python list); `image_embedding`: the image block behind the placeholder, and `pixels` a
+    host copy of the pixel tensor it was encoded from (`UniBind.generate` keeps both, and skips the encoder when the pixels come again);
+    `last_reused` / `last_prefilled`: positions of the most recent call.  Memory: max_positions x d x 2 (K, V) x layers x 2 B ("bf16"), or
+    1 B + 1/128 B ("fp8": codes and one scale byte per head row of 128), held as long as the object lives."""
+
+    def __init__(self, model_text, kv_cache="bf16", max_positions=None):
+        check_kv_cache(model_text, kv_cache, 1)
+        table = int(model_text.cos.shape[0])
+        self.model, self.kv_cache, self.max_positions = model_text, kv_cache, table if max_positions is None else int(max_positions)
+        if not 1 <= self.max_positions <= table:
+            raise ValueError(f"max_positions={max_positions!r}: from 1 to the {table} positions of the RoPE table")
+        self.caches = None
+        self.reset()
+
+    def reset(self):
+        """forget the conversation (the cache tensors stay allocated)"""
+        self.ids, self.length, self.image_embedding, self.pixels = [], 0, None, None
+        self.last_reused = self.last_prefilled = 0
+
+    def check(self, m, input_ids, attention_mask, num_beams, kv_cache, max_new_tokens, NI):
+        """What a call with this cache cannot be raises here, before anything is allocated or changed.  kv_cache: the call's argument or
+        None; NI: positions of the image block of this call (None: no embedding yet, the placeholder then counts as one position)."""
+        if m is not self.model:
+            raise ValueError(f"prefix_cache belongs to another model ({type(self.model).__name__} at {id(self.model):#x}, this one is at {id(m):#x})")
+        if kv_cache is not None and kv_cache != self.kv_cache:
+            raise ValueError(f"kv_cache={kv_cache!r} disagrees with the prefix cache, which holds kv_cache={self.kv_cache!r}")
+        if input_ids.dim() != 2 or int(input_ids.shape[0]) != 1:
+            raise ValueError(f"prefix_cache holds one conversation: batch 1, got input_ids of shape {tuple(input_ids.shape)}")
+        if int(num_beams) != 1:
+            raise ValueError(f"prefix_cache with num_beams={num_beams!r}: beam search replicates and reorders the cache rows, it starts from an empty cache")
+        if attention_mask is not None and not bool(attention_mask.bool().all()):
+            raise ValueError(f"prefix_cache with an attention_mask that hides {int((~attention_mask.bool()).sum())} positions: cached positions "
+                             "are all visible (no padding)")
+        ids = input_ids[0].tolist()
+        n_img = ids.count(IMAGE_PLACEHOLDER)
+        if n_img > 1:
+            raise ValueError(f"prefix_cache with {n_img} <image> placeholders in the prompt: one image per conversation")
+        S0 = len(ids) + n_img * ((NI or 1) - 1)
+        if S0 + int(max_new_tokens) > self.max_positions:
+            raise ValueError(f"prompt ({S0}) + max_new_tokens ({max_new_tokens}) exceeds the {self.max_positions} positions of the prefix cache")
+        return ids
+
+    def begin(self, ids, image_embedding):
+        """Start a call whose prompt is `ids` with image block `image_embedding` (or None): -> the positions it reuses.  The cache is rolled
+        back to them HERE, before the prefill writes anything: a call that dies half way leaves a valid, shorter cache."""
+        old = self.image_embedding
+        same = image_embedding is None or image_embedding is old or (old is not None and old.shape == image_embedding.shape and
+                                                                     bool(torch.equal(old, image_embedding)))
+        NI = 1 if image_embedding is None else int(image_embedding.shape[1])
+        tokens, reuse = match_prefix(self.ids, ids, NI, same)
+        self.ids, self.length = self.ids[:tokens], reuse
+        if not same:
+            self.image_embedding, self.pixels = image_embedding, None
+        if self.caches is None:
+            self.caches = alloc_kv(self.model, self.max_positions, self.kv_cache)
+        return reuse
+
+    def commit(self, ids, new_ids, S0, reuse):
+        """the call emitted `new_ids` behind the prompt `ids` of S0 positions: every token but the last was fed, and is cached"""
+        self.ids, self.length = list(ids) + list(new_ids[:-1]), S0 + len(new_ids) - 1
+        self.last_reused, self.last_prefilled = reuse, S0 - reuse
+
+
 # ------------------------------------------------------------------------------------------------- the GEMM step (prefill, batch > 16)
-def layer_step(m, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None, int8=False):
+def layer_step(m, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None, int8=False, scratch=None):
     """One decoder layer over S_new new positions per sequence behind `ctx` cached ones (prefill: ctx = 0).  li = the layer's index, under
     adapters="live" or int8: the linears are the training forward's (`_lin` / `_gu_fwd`; dropout is off) - adapters on the bf16 base weights,
-    or with int8 (weights="int8" only) `hk.int8_linear` on the int8 rows with the adapters of a live store on top."""
+    or with int8 (weights="int8" only) `hk.int8_linear` on the int8 rows with the adapters of a live store on top.
+
+    The e4m3 cache (four tensors) behind a context, ctx > 0 (generate(prefix_cache=...)): `scratch` = two bf16 tensors [B * (ctx + S_new), d]
+    of the caller (`gemm_logits` makes them once for all layers).  The `ctx` cached K / V rows are dequantised into them
+    (`hk.kv8_dequant_rows`: exact), the bf16 rows of the new positions copied behind, and `attn_fwd` - the kernel of the bf16 path - runs
+    over the scratch (desc: kv_off = b * (ctx + S_new), kv_len = ctx + S_new, causal offset ctx).  The rule: the new positions attend EACH
+    OTHER in exact bf16, as the positions of any prompt do, and the cached positions THROUGH THE CODES, as the single-token step does."""
     d, H, hd, ff = m.d, m.heads, m.hd, m.ff
     M = x.shape[0]
     i8 = (lambda name: (L[name + "i8"], L[name + "i8s"])) if int8 else (lambda name: None)
@@ -148,16 +241,28 @@ def layer_step(m, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None
         qkv = m._lin(li, "qkv", h, L["qkv_w"], rope=(S_new, ctx), i8=i8("qkv_w"))
     o = torch.empty((M, d), device=m.device, dtype=torch.bfloat16)
     if len(cache) == 4:
-        # kv_cache="fp8", prefill only: attention reads the exact bf16 K / V of the prompt straight out of `qkv` (desc: kv_off = b * S_new),
-        # so the prompt's logits are those of the bf16-cache mode bit for bit; the rows enter the cache as codes + scale bytes
-        assert ctx == 0, "the kv8 cache has no multi-row step after the prefill (generate() rejects batch > 16)"
+        # kv_cache="fp8", prefill: attention reads the exact bf16 K / V of the prompt straight out of `qkv` (desc: kv_off = b * S_new),
+        # so the prompt's logits are those of the bf16-cache mode bit for bit; the rows enter the cache as codes + scale bytes.
+        # Behind a context (ctx > 0) the cached rows are read back through the caller's scratch; without one there is no such step
+        assert ctx == 0 or scratch is not None, "the kv8 cache has no multi-row step after the prefill (generate() rejects batch > 16)"
         kc8, vc8, ks, vs = cache
-        hk.attn_fwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True,
-                    1.0 / math.sqrt(hd), key_mask=kmask)
+        if ctx == 0:
+            hk.attn_fwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True,
+                        1.0 / math.sqrt(hd), key_mask=kmask)
+        else:
+            kb, vb = scratch
+            row_b, n = d * 2, ctx + S_new
+            for b in range(B):
+                src = qkv.data_ptr() + b * S_new * 3 * row_b
+                hk.kv8_dequant_rows(kc8, ks, b * max_ctx, ctx, H, kb[b * n:(b + 1) * n])
+                hk.kv8_dequant_rows(vc8, vs, b * max_ctx, ctx, H, vb[b * n:(b + 1) * n])
+                hk.copy_2d(kb.data_ptr() + (b * n + ctx) * row_b, row_b, src + row_b, 3 * row_b, row_b, S_new)
+                hk.copy_2d(vb.data_ptr() + (b * n + ctx) * row_b, row_b, src + 2 * row_b, 3 * row_b, row_b, S_new)
+            hk.attn_fwd(qkv[:, :d], kb, vb, o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True, 1.0 / math.sqrt(hd), key_mask=kmask)
         for b in range(B):
             rows = qkv[b * S_new:(b + 1) * S_new]
-            hk.kv8_quant_rows(rows[:, d:2 * d], kc8, ks, b * max_ctx, H)
-            hk.kv8_quant_rows(rows[:, 2 * d:], vc8, vs, b * max_ctx, H)
+            hk.kv8_quant_rows(rows[:, d:2 * d], kc8, ks, b * max_ctx + ctx, H)
+            hk.kv8_quant_rows(rows[:, 2 * d:], vc8, vs, b * max_ctx + ctx, H)
     else:
         kc, vc = cache
         row_b = d * 2
@@ -180,11 +285,15 @@ def layer_step(m, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None
 def gemm_logits(m, x, B, S, ctx, caches, row_stride, kv8, kmask, lora, weights):
     """S new positions per sequence (rows of x) behind `ctx` cached ones through the GEMM path -> fp32 logits [B, V] of the last one: the
     prefill (ctx = 0) and the step of a batch > 16.  Sequence b owns the cache rows from b * row_stride (`num_beams * max_ctx` under beams).
-    kv8, prefill only: the attention reads K / V out of the qkv buffer itself, where sequence b starts at row b * S."""
+    kv8: the attention reads K / V out of the qkv buffer itself, where sequence b starts at row b * S (prefill), or behind a context out of
+    two bf16 scratch tensors made here for all layers, where sequence b starts at row b * (ctx + S) (see `layer_step`)."""
     i8 = int8_gemm(weights)
-    desc = hk.make_desc([(b * S, S, b * (S if kv8 else row_stride), ctx + S, ctx + S, ctx) for b in range(B)], m.device)
+    desc = hk.make_desc([(b * S, S, b * (ctx + S if kv8 else row_stride), ctx + S, ctx + S, ctx) for b in range(B)], m.device)
+    step_kw = {}
+    if kv8 and ctx > 0:
+        step_kw["scratch"] = tuple(torch.empty((B * (ctx + S), m.d), device=m.device, dtype=torch.bfloat16) for _ in range(2))
     for li, (L, cache) in enumerate(zip(m.p["layers"], caches)):
-        x = m._layer_step(L, x, B, S, ctx, cache, desc, row_stride, kmask, li=li if lora is not None or i8 else None, int8=i8)
+        x = m._layer_step(L, x, B, S, ctx, cache, desc, row_stride, kmask, li=li if lora is not None or i8 else None, int8=i8, **step_kw)
     hn = hk.rmsnorm_fwd(x.view(B, S, -1)[:, -1].contiguous(), m.p["norm_w"], m.eps)
     return hk.gemm_nt(hn, m.p["lm_head"], out_f32=True)
 
@@ -356,7 +465,8 @@ def warp_logits(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[
 def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p=None, top_k=None,
                   max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id=None, return_logits=False,
                   use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1, length_penalty=1.0,
-                  early_stopping=False, return_beam_scores=False, num_return_sequences=1, live_lora=False, kv_cache="bf16", **_kw):
+                  early_stopping=False, return_beam_scores=False, num_return_sequences=1, live_lora=False, kv_cache="bf16", prefix_cache=None,
+                  **_kw):
     """TextModal.generate (text_modal.py:528-627): prefill over the spliced embeddings, then one token at a time with a KV cache; returns only
     the NEW token ids [B, n_new] (HF generate started from inputs_embeds).  Greedy (the evaluation scripts' mode) runs entirely in HIP kernels;
     with do_sample=True the fp32 logits go through HF's temperature / top-k / top-p warpers and one multinomial draw per token.  The step is a
@@ -367,9 +477,20 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
     `repetition_penalty != 1` (HF RepetitionPenaltyLogitsProcessor over the tokens generated so far in this call) exists in that kernel only
     and routes every pick through it whatever `sampler` says: mode 0 when sampling, mode 1 (first maximum of the penalised logits) when greedy.
     With `eos_token_id` set the pad replacement of finished rows and the host's check still run between the pick and `decode_emit`; the kernel
-    has then already set the drawn token's bit in the seen bitmap of a finished row, which nothing reads any more."""
+    has then already set the drawn token's bit in the seen bitmap of a finished row, which nothing reads any more.
+
+    prefix_cache = a `PrefixCache` (batch 1, no beams): the caches are its own and outlive the call.  The prompt is matched against what
+    they hold (`match_prefix`), only the positions behind the common prefix are prefilled (`gemm_logits` with ctx = the reused positions),
+    and the token loop runs as ever, on a session over the cache's rows.  The new positions attend each other in exact bf16, as the
+    positions of any prompt do; they attend the reused ones through what the cache holds - bf16 rows, or with kv_cache="fp8" the codes,
+    as the single-token step does (`layer_step`).  On return the cache holds the prompt and every emitted token but the last."""
     if sampler not in ("torch", "device"):
         raise ValueError(f"sampler={sampler!r}: expected 'torch' or 'device'")
+    pc = prefix_cache
+    if pc is not None:   # rejections first: nothing is allocated or changed before them
+        if image_embedding is None:
+            image_embedding = pc.image_embedding
+        prompt = pc.check(m, input_ids, attention_mask, num_beams, kv_cache, max_new_tokens, None if image_embedding is None else image_embedding.shape[1])
     if int(num_beams) != 1:
         return m._generate_beam(input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer,
                                 eos_token_id, return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty,
@@ -381,8 +502,13 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
         streamer.put(input_ids.cpu())  # transformers.TextStreamer protocol: the first put() is the prompt, which skip_prompt drops
     embeds, _, mask, _ = m.prepare_inputs_for_multimodal(input_ids, attention_mask, None, image_embedding)
     B, S0, d = embeds.shape
-    max_ctx, kmask = decode_context(m, mask, B, S0, max_new_tokens)
-    caches = m._alloc_kv(B * max_ctx, kv_cache)
+    if pc is None:
+        max_ctx, kmask = decode_context(m, mask, B, S0, max_new_tokens)
+        caches, reuse = m._alloc_kv(B * max_ctx, kv_cache), 0
+    else:   # the cache's own rows, all of them visible; it is rolled back to the reused positions before the prefill writes behind them
+        max_ctx, kmask = pc.max_positions, None
+        reuse = pc.begin(prompt, image_embedding)
+        caches = pc.caches
     dev, lora = m.device, m.lora if live_lora else None   # adapters="live": the store the session and the GEMM steps read
     s, seen, step_dev = None, None, None
 
@@ -411,7 +537,8 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
         return torch.multinomial(torch.softmax(warp_logits(logits, temperature, top_k, top_p), -1), 1).squeeze(1)
 
     # ---- prefill (GEMM path) -> logits of the last prompt position -> first new token
-    logits = gemm_logits(m, embeds.reshape(B * S0, d), B, S0, 0, caches, max_ctx, kv_cache == "fp8", kmask, lora, weights)
+    # (behind the `reuse` positions a prefix cache already holds: B = 1, the rows of embeds[0, reuse:])
+    logits = gemm_logits(m, embeds.reshape(B * S0, d)[reuse:], B, S0 - reuse, reuse, caches, max_ctx, kv_cache == "fp8", kmask, lora, weights)
     all_logits = [logits.clone()] if return_logits else []
     n_done = 0
     nxt = pick(logits)
@@ -474,6 +601,8 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
             if host_checks:
                 stop = host_step(torch.stack(out_ids, 1), logits)
         ids = torch.stack(out_ids, 1)
+    if pc is not None:
+        pc.commit(prompt, ids[0].tolist(), S0, reuse)
     if streamer is not None:
         streamer.end()
     return (ids, torch.stack(all_logits, 1)) if return_logits else ids

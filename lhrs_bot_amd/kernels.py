@@ -953,6 +953,20 @@ def kv8_quant_rows(src, codes, scales, row0, H):
                "kv8_quant_rows")
 
 
+def kv8_dequant_rows(codes, scales, row0, n, H, out):
+    """lhrs_kv8_dequant_rows: the cache rows row0 .. row0 + n - 1 (codes uint8 [rows, H * 128], scales uint8 [rows, H]) -> the first n rows
+    of `out`, bf16 [>= n, H * 128] with any row stride: e4m3(code) * 2^(byte - 127), exact in bf16"""
+    _req(codes, torch.uint8, "codes")
+    _req(scales, torch.uint8, "scales")
+    _req(out, torch.bfloat16, "out")
+    row0, n = int(row0), int(n)
+    assert out.dim() == 2 and out.shape[1] == H * 128 and out.stride(1) == 1 and out.shape[0] >= n and codes.is_contiguous() and scales.is_contiguous()
+    assert codes.shape[1] == H * 128 and scales.shape[1] == H and 0 <= row0 and row0 + n <= codes.shape[0] and codes.shape[0] == scales.shape[0]
+    _lib.check(_L().lhrs_kv8_dequant_rows(codes.data_ptr(), scales.data_ptr(), row0, n, H, out.data_ptr(), out.stride(0), _stream()),
+               "kv8_dequant_rows")
+    return out
+
+
 def decode_attn_kv8(qkv, kc8, vc8, ks, vs, cos_t, sin_t, pos, out, B, H, D, max_ctx, scale, nsplit=1, part=None, tickets=None, key_mask=None,
                     cs=None):
     """decode_attn / decode_attn_split on the kv8 caches (lhrs_decode_attn_kv8): kc8 / vc8 uint8 [B * max_ctx, H * 128], ks / vs uint8

@@ -715,6 +715,10 @@ class TextModal:
     def _decode_session(self, B, max_ctx, caches, max_new, weights="bf16", kmask=None, lora=None, kv_cache="bf16"):
         return generation.DecodeSession(self, B, max_ctx, caches, max_new, weights, kmask, lora, kv_cache)
 
+    def new_prefix_cache(self, kv_cache="bf16", max_positions=None):
+        """-> generation.PrefixCache of this model for `generate(prefix_cache=...)`: the KV cache of one conversation, kept between calls"""
+        return generation.PrefixCache(self, kv_cache, max_positions)
+
     def quantize_fp8(self):
         """e4m3 copies (per-output-row scale) of every LLaMA linear for the decode step: 6.7 GB instead of 13.5 GB per token."""
         generation.quantize_fp8(self)
@@ -832,7 +836,8 @@ class TextModal:
     def generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p="default",
                  top_k="default", max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id="default",
                  return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1,
-                 length_penalty=1.0, early_stopping=False, return_beam_scores=False, adapters="merged", kv_cache="bf16", **_kw):
+                 length_penalty=1.0, early_stopping=False, return_beam_scores=False, adapters="merged", kv_cache=None, prefix_cache=None,
+                 **_kw):
         """See `_generate`.  Two things happen here first: (1) `eos_token_id` defaults to the tokenizer's EOS, as HF `generate` stops on
         the generation config's EOS (pass None to disable); (2) if LoRA adapters are attached and not merged, `adapters` says how they run:
         "merged" (default) - on merged COPIES of the affected weights (`_lora_merged_layers`), the base weights come back untouched;
@@ -857,9 +862,25 @@ class TextModal:
         `kv_cache`: "bf16" (default) or "fp8" - e4m3 codes and one e8m0 scale byte per head row (the kv8 format of csrc/decode_attn.hip: half
         the cache memory and stream).  The prefill attends over the exact bf16 K / V of the prompt, so its logits and the first token are those
         of "bf16"; from the second token on the step reads the rounded cache (`hk.decode_attn_kv8`).  Works with every `weights` / `adapters` /
-        sampler mode, left padding and beams; needs head_dim 128 and batch x num_beams <= 16, else ValueError."""
+        sampler mode, left padding and beams; needs head_dim 128 and batch x num_beams <= 16, else ValueError.  None (default): "bf16", or
+        with `prefix_cache` the kind of that cache.
+
+        `prefix_cache`: a `PrefixCache` of this model (`new_prefix_cache`) that keeps the KV cache of a conversation between calls.  The
+        prompt is matched against the cached ids, the common prefix - the image block included when the image embedding is the cached one,
+        which is also used when `image_embedding` is None - is not prefilled again, and on return the cache holds the prompt and every new
+        token but the last.  The new positions attend each other in exact bf16, as the positions of any prompt do, and the reused ones
+        through the cache: bf16 rows, or with an "fp8" cache the e4m3 codes (dequantised exactly by `hk.kv8_dequant_rows`), as the
+        single-token step reads them - so behind an "fp8" prefix the first token is no longer the "bf16" one.  Batch 1, no beams, no
+        padding mask, one placeholder, prompt + max_new_tokens <= `max_positions`; anything else raises ValueError and leaves the cache as it was.
+        Every `weights` / `adapters` / sampler mode works; the cache does not know which produced its rows - `reset()` it when they change."""
         if adapters not in ("merged", "live"):
             raise ValueError(f"adapters={adapters!r}: expected 'merged' or 'live'")
+        if prefix_cache is not None:   # before anything is allocated (the merged copies below) or changed
+            emb = image_embedding if image_embedding is not None else prefix_cache.image_embedding
+            prefix_cache.check(self, input_ids, attention_mask, num_beams, kv_cache, max_new_tokens, None if emb is None else emb.shape[1])
+            kv_cache = prefix_cache.kv_cache
+        elif kv_cache is None:
+            kv_cache = "bf16"
         nb_ = int(num_beams) if int(num_beams) >= 1 else 1
         self._check_kv_cache(kv_cache, int(input_ids.shape[0]) * nb_, nb_)
         if eos_token_id == "default":
@@ -874,7 +895,7 @@ class TextModal:
                   top_k=top_k, max_new_tokens=max_new_tokens, use_cache=use_cache, stopping_criteria=stopping_criteria, streamer=streamer,
                   eos_token_id=eos_token_id, return_logits=return_logits, use_graph=use_graph, weights=weights, sampler=sampler, seed=seed,
                   repetition_penalty=repetition_penalty, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
-                  return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1), kv_cache=kv_cache)
+                  return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1), kv_cache=kv_cache, prefix_cache=prefix_cache)
         if generation.int8_gemm(weights) and not self.base_int8:
             raise ValueError(generation.NO_BASE["int8"][0])
         if self.lora is None:

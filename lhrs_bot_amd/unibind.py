@@ -250,15 +250,38 @@ class UniBind:
     @torch.no_grad()
     def generate(self, input_ids, images=None, do_sample=True, temperature=0.2, max_new_tokens=1024, streamer=None, use_cache=True,
                  stopping_criteria=None, **kwargs):
-        """UniBind.generate (lhrs/models/UniBind.py:214-242): encode the image once, then TextModal.generate."""
+        """UniBind.generate (lhrs/models/UniBind.py:214-242): encode the image once, then TextModal.generate.
+
+        prefix_cache=<new_prefix_cache()>: once per CONVERSATION - the cache keeps the image embedding and a host copy of the pixels it
+        came from; `images` None or `torch.equal` to those pixels skips the ViT and the projector, another image is encoded and makes the
+        cached image block (and everything behind it) unusable.  See `TextModal.generate`."""
         assert hasattr(self, "text"), "text modal is not activate"
-        if "kv_cache" in kwargs:  # what the fp8 cache cannot serve raises before the image is encoded
+        pc = kwargs.get("prefix_cache")
+        if kwargs.get("kv_cache") is not None:  # what the fp8 cache cannot serve raises before the image is encoded
             nb = max(int(kwargs.get("num_beams", 1)), 1)
             self.text._check_kv_cache(kwargs["kv_cache"], int(input_ids.shape[0]) * nb, nb)
-        image_embedding = self.encode_image(images, pool=False) if images is not None else None  # None: text-only turn
-        return self.text.generate(input_ids=input_ids, image_embedding=image_embedding, do_sample=do_sample, temperature=temperature,
-                                  max_new_tokens=max_new_tokens, streamer=streamer, use_cache=use_cache,
-                                  stopping_criteria=stopping_criteria, **kwargs)
+        if pc is None:
+            image_embedding = self.encode_image(images, pool=False) if images is not None else None  # None: text-only turn
+        else:
+            pc.check(self.text, input_ids, kwargs.get("attention_mask"), kwargs.get("num_beams", 1), kwargs.get("kv_cache"), max_new_tokens,
+                     self.rgb_pooler.nq if images is not None or pc.image_embedding is not None else None)   # rejections before the encoder runs
+            pixels = None
+            if images is None or (pc.pixels is not None and torch.is_tensor(images) and images.shape == pc.pixels.shape and
+                                  images.dtype == pc.pixels.dtype and torch.equal(images.cpu(), pc.pixels)):
+                image_embedding = pc.image_embedding
+            else:
+                pixels = images.detach().cpu().clone() if torch.is_tensor(images) else None   # a list of pictures is encoded every time
+                image_embedding = self.encode_image(images, pool=False)
+        out = self.text.generate(input_ids=input_ids, image_embedding=image_embedding, do_sample=do_sample, temperature=temperature,
+                                 max_new_tokens=max_new_tokens, streamer=streamer, use_cache=use_cache,
+                                 stopping_criteria=stopping_criteria, **kwargs)
+        if pc is not None and pixels is not None:
+            pc.pixels = pixels   # of pc.image_embedding, which the call above has stored
+        return out
+
+    def new_prefix_cache(self, kv_cache="bf16", max_positions=None):
+        """-> the KV cache of one conversation for `generate(prefix_cache=...)` (generation.PrefixCache, bound to this model's decoder)"""
+        return self.text.new_prefix_cache(kv_cache, max_positions)
 
     def backward(self, loss_scale: float = 1.0) -> None:
         d_image = self.text.backward(loss_scale, need_input_grad=self.rgb_pooler.requires_grad)
