@@ -315,6 +315,17 @@ int lhrs_sample_rows(const float* logits, long ld, long* out, int n, int V,
                      float repetition_penalty /* 1: off */, unsigned* seen /* [n][(V+31)/32] bitmap, may be NULL iff penalty == 1 */,
                      unsigned long long seed, const int* step_dev /* may be NULL */, long step_host,
                      long long* weights_out /* [n][V], tests only, NULL in the product */, void* stream);
+/* constrained decoding pick (HF generate prefix_allowed_tokens_fn: PrefixConstrainedLogitsProcessor, then argmax), one launch, one workgroup per
+ * row of fp32 logits [n][V], V <= 32768.  The automaton is CSR over int32: off[n_states + 1], tok[n_edges] ascending and unique inside a state,
+ * nxt[n_edges], label[n_states]; state 0 is the start and a state without out-edges is final.  Row r in state s = state[r]: s outside
+ * [0, n_states) or final -> out[r] = pad_token_id and nothing else changes; otherwise e* = the edge of s with the largest logits[r][tok[e]]
+ * (first maximum = lowest token among equals, as lhrs_argmax_rows; NaN compares as -inf; all -inf: the first edge), out[r] = tok[e*],
+ * len[r] += 1, state[r] = nxt[e*], and if that state is final fin[r] = 1, choice[r] = label[nxt[e*]].  score (may be NULL): score[r] +=
+ * logits[r][tok[e*]] - lse(r), lse the fp32 log-sum-exp of the WHOLE row (log_softmax before the mask, as HF); with NULL only the allowed
+ * logits are read.  Every row writes its own slots only. */
+int lhrs_constrain_rows(const float* logits, long ld, long* out, int n, int V, const int* off, const int* tok, const int* nxt, const int* label,
+                        int n_states, int n_edges, int pad_token_id, int* state, int* fin, int* len, int* choice,
+                        float* score /* may be NULL */, void* stream);
 /* beam search (HF generate num_beams > 1, do_sample=False: the web UI's answer_prepare kwargs), three launches per token between the model step
  * and lhrs_decode_emit.  bstate: int32 [4] = {t = tokens generated before this step, done, -, -}; once done is set all three change nothing.
  * hist: int32 [2][rows][max_new] token history of the running beams, buffer t & 1 is current.

@@ -220,6 +220,133 @@ class PrefixCache:
         self.last_reused, self.last_prefilled = reuse, S0 - reuse
 
 
+# ------------------------------------------------------------------------------------------------- constrained decoding
+class TokenAutomaton:
+    """A deterministic automaton over token ids for `generate(constraint=...)`, in CSR form on the device (all int32): `off`
+    [n_states + 1] edge ranges, `tok` [E] edge tokens - ascending and unique inside a state -, `nxt` [E] target states, `label` [n_states]
+    -1 or the caller's index of a final state.  State 0 is the start; a state without out-edges is final.  `pad_token_id` is what rows
+    behind a final state emit, `V` the vocabulary size the tokens were validated for.  Built by `from_edges` (which validates),
+    `choice_automaton` or `vocab_loop_automaton`; `hk.constrain_rows` walks it."""
+
+    def __init__(self, off, tok, nxt, label, pad_token_id, V):
+        self.off, self.tok, self.nxt, self.label, self.pad_token_id, self.V = off, tok, nxt, label, int(pad_token_id), int(V)
+
+    n_states = property(lambda self: int(self.label.numel()))
+    n_edges = property(lambda self: int(self.tok.numel()))
+    device = property(lambda self: self.off.device)
+
+    @classmethod
+    def from_edges(cls, off, tok, nxt, label, pad_token_id, V, device="cpu"):
+        """Host arrays (anything `numpy.asarray` takes) -> the automaton on `device`.  Everything the kernel relies on is checked HERE, before
+        anything is uploaded; cycles are allowed (max_new_tokens bounds the walk)."""
+        import numpy as np
+
+        def ints(a, name):
+            a = np.asarray(a)
+            if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+                raise ValueError(f"TokenAutomaton: {name} must be a 1-d integer array, got shape {a.shape} of {a.dtype}")
+            return a.astype(np.int64)
+        off, tok, nxt, label = ints(off, "off"), ints(tok, "tok"), ints(nxt, "nxt"), ints(label, "label")
+        V, n_states, E = int(V), int(label.size), int(tok.size)
+        if n_states < 1 or off.size != n_states + 1 or nxt.size != E:
+            raise ValueError(f"TokenAutomaton: {n_states} labels need {n_states + 1} offsets (got {off.size}) and one target per edge "
+                             f"({E} tokens, {nxt.size} targets)")
+        if not 1 <= V <= 32768:
+            raise ValueError(f"TokenAutomaton: V={V}: hk.constrain_rows serves 1..32768 tokens")
+        if E >= 1 << 31 or not -(1 << 31) <= int(pad_token_id) < 1 << 31 or (label.size and (label.min() < -(1 << 31) or label.max() >= 1 << 31)):
+            raise ValueError("TokenAutomaton: edge count, labels and pad_token_id must fit int32")
+        if off[0] != 0 or off[-1] != E or bool((np.diff(off) < 0).any()):
+            raise ValueError(f"TokenAutomaton: offsets must rise monotonically from 0 to the {E} edges, got {off[:8].tolist()}... ending in {int(off[-1])}")
+        if E and (tok.min() < 0 or tok.max() >= V):
+            raise ValueError(f"TokenAutomaton: edge tokens must be in [0, {V}), got {int(tok.min())}..{int(tok.max())}")
+        if E and (nxt.min() < 0 or nxt.max() >= n_states):
+            raise ValueError(f"TokenAutomaton: edge targets must be states in [0, {n_states}), got {int(nxt.min())}..{int(nxt.max())}")
+        if off[1] == 0:
+            raise ValueError("TokenAutomaton: state 0, the start, has no edge")
+        inner = np.ones(E, dtype=bool)           # edges that have a predecessor in the same state
+        inner[off[:-1][off[:-1] < E]] = False
+        bad = np.nonzero(inner[1:] & (tok[1:] <= tok[:-1]))[0]
+        if bad.size:
+            e = int(bad[0]) + 1
+            raise ValueError(f"TokenAutomaton: the edge tokens of a state must be ascending and unique (the tie rule is the lowest token): "
+                             f"state {int(np.searchsorted(off, e, side='right')) - 1} has {int(tok[e - 1])} before {int(tok[e])}")
+        def up(a):
+            t = torch.from_numpy(a.astype(np.int32))
+            return hk.h2d(t, device) if torch.device(device).type == "cuda" else t
+        return cls(up(off), up(tok), up(nxt), up(label), pad_token_id, V)
+
+
+def choice_automaton(token_lists, eos_token_id, pad_token_id, V, device="cpu"):
+    """The trie of the given token-id sequences, each followed by `eos_token_id`: the final state behind choice i has label i.  A choice
+    may be a strict prefix of another (the EOS edge tells them apart); duplicate or empty choices raise ValueError."""
+    lists = [[int(t) for t in c] for c in token_lists]
+    if not lists:
+        raise ValueError("choice_automaton: no choices")
+    children, label, seen = [{}], [-1], {}
+    for i, c in enumerate(lists):
+        if not c:
+            raise ValueError(f"choice_automaton: choice {i} is empty")
+        if tuple(c) in seen:
+            raise ValueError(f"choice_automaton: choices {seen[tuple(c)]} and {i} are the same token sequence {c}")
+        if int(eos_token_id) in c:
+            raise ValueError(f"choice_automaton: choice {i} contains the EOS token {eos_token_id}, which ends a choice")
+        seen[tuple(c)] = i
+        s = 0
+        for t in c + [int(eos_token_id)]:
+            if t not in children[s]:
+                children.append({})
+                label.append(-1)
+                children[s][t] = len(children) - 1
+            s = children[s][t]
+        label[s] = i
+    off, tok, nxt = [0], [], []
+    for ch in children:
+        for t in sorted(ch):
+            tok.append(t)
+            nxt.append(ch[t])
+        off.append(len(tok))
+    return TokenAutomaton.from_edges(off, tok, nxt, label, pad_token_id, V, device)
+
+
+def vocab_loop_automaton(V, eos_token_id=None, pad_token_id=0, device="cpu"):
+    """One state whose V edges loop to itself: the pick is then plain greedy.  With an EOS that edge leads to a final state (label 0)
+    instead, which gives greedy decoding its EOS handling on the device."""
+    import numpy as np
+    tok, nxt = np.arange(int(V), dtype=np.int64), np.zeros(int(V), dtype=np.int64)
+    if eos_token_id is None:
+        return TokenAutomaton.from_edges([0, V], tok, nxt, [-1], pad_token_id, V, device)
+    if not 0 <= int(eos_token_id) < int(V):
+        raise ValueError(f"vocab_loop_automaton: eos_token_id={eos_token_id} is outside [0, {V})")
+    nxt[int(eos_token_id)] = 1
+    return TokenAutomaton.from_edges([0, V, V], tok, nxt, [-1, 0], pad_token_id, V, device)
+
+
+def _same_device(a, b) -> bool:
+    a, b = torch.device(a), torch.device(b)
+    index = lambda d: d.index if d.index is not None or d.type != "cuda" else torch.cuda.current_device()  # noqa: E731
+    return a.type == b.type and index(a) == index(b)
+
+
+def check_constraint(m, constraint, return_choices=False, do_sample=False, num_beams=1, repetition_penalty=1.0, prefix_cache=None):
+    """generate(constraint=..., return_choices=...): what the constrained pick cannot be raises here, before anything is allocated"""
+    if constraint is None:
+        if return_choices:
+            raise ValueError("return_choices=True needs a constraint: the choice is the label of the automaton's final state")
+        return
+    if not isinstance(constraint, TokenAutomaton):
+        raise ValueError(f"constraint={type(constraint).__name__}: expected a TokenAutomaton (choice_constraint / choice_automaton / from_edges)")
+    for bad, why in ((do_sample, "constraint with do_sample=True: the constrained pick is greedy (the best allowed token)"),
+                     (int(num_beams) != 1, f"constraint with num_beams={num_beams!r}: beams over an automaton are not implemented"),
+                     (float(repetition_penalty) != 1.0, f"constraint with repetition_penalty={repetition_penalty!r}: the penalty lives in the sampling kernel, "
+                                                        "which knows no automaton"),
+                     (prefix_cache is not None, "constraint with prefix_cache: the pads behind a final state must not enter a kept cache"),
+                     (constraint.V != m.vocab, f"the constraint was validated for a vocabulary of {constraint.V}, the model has {m.vocab}")):
+        if bad:
+            raise ValueError(why)
+    if not _same_device(constraint.device, m.device):
+        raise ValueError(f"the constraint lives on {constraint.device}, the model on {m.device}")
+
+
 # ------------------------------------------------------------------------------------------------- the GEMM step (prefill, batch > 16)
 def layer_step(m, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None, int8=False, scratch=None):
     """One decoder layer over S_new new positions per sequence behind `ctx` cached ones (prefill: ctx = 0).  li = the layer's index, under
@@ -466,7 +593,7 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
                   max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id=None, return_logits=False,
                   use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1, length_penalty=1.0,
                   early_stopping=False, return_beam_scores=False, num_return_sequences=1, live_lora=False, kv_cache="bf16", prefix_cache=None,
-                  **_kw):
+                  constraint=None, return_choices=False, **_kw):
     """TextModal.generate (text_modal.py:528-627): prefill over the spliced embeddings, then one token at a time with a KV cache; returns only
     the NEW token ids [B, n_new] (HF generate started from inputs_embeds).  Greedy (the evaluation scripts' mode) runs entirely in HIP kernels;
     with do_sample=True the fp32 logits go through HF's temperature / top-k / top-p warpers and one multinomial draw per token.  The step is a
@@ -483,7 +610,15 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
     they hold (`match_prefix`), only the positions behind the common prefix are prefilled (`gemm_logits` with ctx = the reused positions),
     and the token loop runs as ever, on a session over the cache's rows.  The new positions attend each other in exact bf16, as the
     positions of any prompt do; they attend the reused ones through what the cache holds - bf16 rows, or with kv_cache="fp8" the codes,
-    as the single-token step does (`layer_step`).  On return the cache holds the prompt and every emitted token but the last."""
+    as the single-token step does (`layer_step`).  On return the cache holds the prompt and every emitted token but the last.
+
+    constraint = a `TokenAutomaton` (greedy only, no beams, penalty or prefix cache): every pick, the prefill's included, is ONE launch of
+    `hk.constrain_rows` where `argmax_rows` runs otherwise - the best token among the out-edges of the row's state, and the walk along it.
+    The model step, the graph and `decode_emit` are as ever.  Rows behind a final state emit pad_token_id; the host reads the rows' `fin`
+    every fourth token (every token on the host path of eos / stopping criteria / streamer) and stops when all are final; the ids are cut to
+    the longest row, its EOS included.  return_choices=True appends (choice [B] int64: the final state's label, -1 where max_new_tokens ran
+    out first; score [B] fp32: the sum of the picked tokens' log-probabilities over the full vocabulary) - only then is the score computed."""
+    check_constraint(m, constraint, return_choices, do_sample, num_beams, repetition_penalty, prefix_cache)
     if sampler not in ("torch", "device"):
         raise ValueError(f"sampler={sampler!r}: expected 'torch' or 'device'")
     pc = prefix_cache
@@ -511,6 +646,7 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
         caches = pc.caches
     dev, lora = m.device, m.lora if live_lora else None   # adapters="live": the store the session and the GEMM steps read
     s, seen, step_dev = None, None, None
+    cs = hk.ConstraintState(B, dev) if constraint is not None else None
 
     def session():
         s = m._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora, kv_cache)
@@ -524,12 +660,19 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
         if B <= 16:  # the draw's step counter is the session's count of emitted tokens, on the device
             s = session()
             step_dev = s.state[1:2]
+    elif cs is not None and B <= 16:
+        s = session()
 
     def pick_device(logits, out=None, step_host=0):
         return hk.sample_rows(logits, out, mode=0 if do_sample else 1, temperature=temperature, top_k=top_k, top_p=top_p,
                               repetition_penalty=pen, seen=seen, seed=seed, step_dev=step_dev, step_host=step_host)
 
+    def pick_constrained(logits, out=None):
+        return hk.constrain_rows(logits, constraint, cs, out, score=return_choices)
+
     def pick(logits):
+        if cs is not None:
+            return pick_constrained(logits, None if s is None else s.next_ids)
         if device_pick:
             return pick_device(logits, None if s is None else s.next_ids, 0 if s is not None else n_done)
         if not do_sample:
@@ -554,6 +697,8 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
             finished |= ids_so_far[:, -1] == eos_token_id
             if bool(finished.all()):
                 return True
+        if cs is not None and bool(cs.fin.all()):
+            return True
         return stopping_criteria is not None and any(c(ids_so_far, lg) for c in stopping_criteria)
 
     n_done = 1
@@ -571,7 +716,9 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
                 step_or_replay(s, s.enqueue, use_graph, n_done)
                 if return_logits:
                     all_logits.append(s.logits.clone())
-                if device_pick:
+                if cs is not None:
+                    pick_constrained(s.logits, s.next_ids)
+                elif device_pick:
                     pick_device(s.logits, s.next_ids)
                 elif do_sample:
                     s.next_ids.copy_(pick(s.logits))
@@ -583,6 +730,8 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
                 n_done += 1
                 if host_checks:
                     stop = host_step(s.out_ids[:, :n_done], s.logits)
+                elif cs is not None and n_done % 4 == 0:   # as generate_beam reads its done word
+                    stop = bool(cs.fin.all())
         torch.cuda.current_stream().wait_stream(side)
         ids = s.out_ids[:, :n_done].clone()
     else:
@@ -600,12 +749,18 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
             n_done += 1
             if host_checks:
                 stop = host_step(torch.stack(out_ids, 1), logits)
+            elif cs is not None and n_done % 4 == 0:
+                stop = bool(cs.fin.all())
         ids = torch.stack(out_ids, 1)
+    if cs is not None:   # the longest row with its EOS: the columns behind it (the picks since the last look at `fin`) hold pads only
+        n_done = int(cs.len.max().item())
+        ids, all_logits = ids[:, :n_done].contiguous(), all_logits[:n_done]
     if pc is not None:
         pc.commit(prompt, ids[0].tolist(), S0, reuse)
     if streamer is not None:
         streamer.end()
-    return (ids, torch.stack(all_logits, 1)) if return_logits else ids
+    out = (ids,) + ((torch.stack(all_logits, 1),) if return_logits else ()) + ((cs.choice.to(torch.int64), cs.score.clone()) if return_choices else ())
+    return out if len(out) > 1 else out[0]
 
 
 def generate_beam(m, input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer, eos_token_id,

@@ -725,6 +725,46 @@ def sample_rows(logits_f32, out=None, *, mode=0, temperature=1.0, top_k=0, top_p
     return out
 
 
+class ConstraintState:
+    """Per-row device state of a walk over a token automaton (include/lhrs_hip.h: lhrs_constrain_rows): `state` (0 = the start), `fin`
+    (1 once the row reached a final state), `len` (tokens picked so far, the EOS included), `choice` (the final state's label, -1 before)
+    all int32 [n], and `score` fp32 [n], the sum of the picked tokens' log-probabilities (only moved when the pick is asked to)."""
+
+    def __init__(self, n, device):
+        i32 = dict(device=device, dtype=torch.int32)
+        self.n = int(n)
+        self.state, self.fin, self.len = torch.zeros(n, **i32), torch.zeros(n, **i32), torch.zeros(n, **i32)
+        self.choice = torch.full((n,), -1, **i32)
+        self.score = torch.zeros(n, device=device, dtype=torch.float32)
+
+
+def constrain_rows(logits_f32, automaton, st: ConstraintState, out=None, *, score=False):
+    """lhrs_constrain_rows: per row of fp32 logits [n, V] the first maximum among the out-edges of the row's state in `automaton` (a
+    generation.TokenAutomaton: off / tok / nxt / label int32 on the device, pad_token_id, V), the walk along that edge in `st`, and with
+    `score` the picked token's log-probability over the whole row added to st.score.  Rows in a final or invalid state get pad_token_id."""
+    n, V = logits_f32.shape
+    _req(logits_f32, torch.float32, "logits")
+    assert logits_f32.stride(1) == 1
+    out = torch.empty(n, device=logits_f32.device, dtype=torch.int64) if out is None else out
+    _req(out, torch.int64, "out")
+    a = automaton
+    for name in ("off", "tok", "nxt", "label"):
+        _req(getattr(a, name), torch.int32, "automaton." + name)
+        assert getattr(a, name).is_contiguous(), f"automaton.{name} is not contiguous"
+    for name in ("state", "fin", "len", "choice"):
+        _req(getattr(st, name), torch.int32, "ConstraintState." + name)
+    _req(st.score, torch.float32, "ConstraintState.score")
+    n_states, n_edges = a.label.numel(), a.tok.numel()
+    assert V == a.V, f"logits of {V} columns for an automaton validated for V={a.V}"
+    assert a.off.numel() == n_states + 1 and a.nxt.numel() == n_edges, "automaton arrays disagree in length"
+    assert st.n == n and out.numel() == n and out.is_contiguous(), f"ConstraintState of {st.n} rows / out of {out.numel()} for {n} rows of logits"
+    _lib.check(_L().lhrs_constrain_rows(logits_f32.data_ptr(), logits_f32.stride(0), out.data_ptr(), n, V, a.off.data_ptr(), a.tok.data_ptr(),
+                                        a.nxt.data_ptr(), a.label.data_ptr(), n_states, n_edges, int(a.pad_token_id), st.state.data_ptr(),
+                                        st.fin.data_ptr(), st.len.data_ptr(), st.choice.data_ptr(), st.score.data_ptr() if score else None,
+                                        _stream()), "constrain_rows")
+    return out
+
+
 class BeamState:
     """Device state of one beam search over B rows x nb beams (include/lhrs_hip.h: lhrs_beam_step), initialised as HF's _beam_search does."""
 

@@ -715,6 +715,25 @@ class TextModal:
     def _decode_session(self, B, max_ctx, caches, max_new, weights="bf16", kmask=None, lora=None, kv_cache="bf16"):
         return generation.DecodeSession(self, B, max_ctx, caches, max_new, weights, kmask, lora, kv_cache)
 
+    def choice_constraint(self, choices, eos_token_id=None):
+        """-> generation.TokenAutomaton on this model's device for `generate(constraint=...)`: the answer is exactly one of `choices`
+        (strings, tokenised without special tokens, or token-id lists) followed by EOS (default: the tokenizer's); choice i ends in the
+        final state of label i."""
+        tok = self.tokenizer
+        eos = getattr(tok, "eos_token_id", None) if eos_token_id is None else eos_token_id
+        if eos is None:
+            raise ValueError("choice_constraint: the tokenizer has no eos_token_id - pass one")
+        lists = []
+        for c in choices:
+            if isinstance(c, str):
+                ids = list(tok(c, add_special_tokens=False).input_ids)
+                if ids and ids[0] == getattr(tok, "bos_token_id", None):   # a tokenizer that adds its BOS whatever it is told (SyntheticTokenizer)
+                    ids = ids[1:]
+                c = ids
+            lists.append([int(t) for t in c])
+        pad = getattr(tok, "pad_token_id", None)
+        return generation.choice_automaton(lists, int(eos), 0 if pad is None else int(pad), self.vocab, self.device)
+
     def new_prefix_cache(self, kv_cache="bf16", max_positions=None):
         """-> generation.PrefixCache of this model for `generate(prefix_cache=...)`: the KV cache of one conversation, kept between calls"""
         return generation.PrefixCache(self, kv_cache, max_positions)
@@ -837,7 +856,7 @@ class TextModal:
                  top_k="default", max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id="default",
                  return_logits=False, use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1,
                  length_penalty=1.0, early_stopping=False, return_beam_scores=False, adapters="merged", kv_cache=None, prefix_cache=None,
-                 **_kw):
+                 constraint=None, return_choices=False, **_kw):
         """See `_generate`.  Two things happen here first: (1) `eos_token_id` defaults to the tokenizer's EOS, as HF `generate` stops on
         the generation config's EOS (pass None to disable); (2) if LoRA adapters are attached and not merged, `adapters` says how they run:
         "merged" (default) - on merged COPIES of the affected weights (`_lora_merged_layers`), the base weights come back untouched;
@@ -872,9 +891,20 @@ class TextModal:
         through the cache: bf16 rows, or with an "fp8" cache the e4m3 codes (dequantised exactly by `hk.kv8_dequant_rows`), as the
         single-token step reads them - so behind an "fp8" prefix the first token is no longer the "bf16" one.  Batch 1, no beams, no
         padding mask, one placeholder, prompt + max_new_tokens <= `max_positions`; anything else raises ValueError and leaves the cache as it was.
-        Every `weights` / `adapters` / sampler mode works; the cache does not know which produced its rows - `reset()` it when they change."""
+        Every `weights` / `adapters` / sampler mode works; the cache does not know which produced its rows - `reset()` it when they change.
+
+        `constraint`: a `TokenAutomaton` (`choice_constraint`, or the builders of generation.py) - the answer is a path through it: every
+        pick is the best ALLOWED token (`hk.constrain_rows`), rows that reached a final state emit pad_token_id, and the call ends when
+        all rows are final (the ids are cut to the longest row, its EOS included) or at max_new_tokens.  The automaton carries its own
+        EOS edges, so the "default" `eos_token_id` is None here: the host then looks at the rows only every fourth token.  Greedy only:
+        do_sample, num_beams != 1, repetition_penalty != 1 and prefix_cache raise ValueError, as does an automaton of another vocabulary
+        size or device.  `return_choices=True` appends (choice [B] int64 - the label of the final state, -1 where max_new_tokens ran out
+        first -, score [B] fp32 - the sum of the picked tokens' log-probabilities, normalised over the full vocabulary as HF's scores are)."""
         if adapters not in ("merged", "live"):
             raise ValueError(f"adapters={adapters!r}: expected 'merged' or 'live'")
+        generation.check_constraint(self, constraint, return_choices, do_sample, num_beams, repetition_penalty, prefix_cache)
+        if constraint is not None and eos_token_id == "default":
+            eos_token_id = None
         if prefix_cache is not None:   # before anything is allocated (the merged copies below) or changed
             emb = image_embedding if image_embedding is not None else prefix_cache.image_embedding
             prefix_cache.check(self, input_ids, attention_mask, num_beams, kv_cache, max_new_tokens, None if emb is None else emb.shape[1])
@@ -895,7 +925,8 @@ class TextModal:
                   top_k=top_k, max_new_tokens=max_new_tokens, use_cache=use_cache, stopping_criteria=stopping_criteria, streamer=streamer,
                   eos_token_id=eos_token_id, return_logits=return_logits, use_graph=use_graph, weights=weights, sampler=sampler, seed=seed,
                   repetition_penalty=repetition_penalty, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
-                  return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1), kv_cache=kv_cache, prefix_cache=prefix_cache)
+                  return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1), kv_cache=kv_cache, prefix_cache=prefix_cache,
+                  constraint=constraint, return_choices=return_choices)
         if generation.int8_gemm(weights) and not self.base_int8:
             raise ValueError(generation.NO_BASE["int8"][0])
         if self.lora is None:

@@ -11,7 +11,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, generation
 from .pooler import AttnPooler
 from .text import TextModal
 from .vision import VisionModal
@@ -257,6 +257,8 @@ class UniBind:
         cached image block (and everything behind it) unusable.  See `TextModal.generate`."""
         assert hasattr(self, "text"), "text modal is not activate"
         pc = kwargs.get("prefix_cache")
+        generation.check_constraint(self.text, kwargs.get("constraint"), kwargs.get("return_choices", False), do_sample, kwargs.get("num_beams", 1),
+                                    kwargs.get("repetition_penalty", 1.0), pc)   # rejections before the encoder runs
         if kwargs.get("kv_cache") is not None:  # what the fp8 cache cannot serve raises before the image is encoded
             nb = max(int(kwargs.get("num_beams", 1)), 1)
             self.text._check_kv_cache(kwargs["kv_cache"], int(input_ids.shape[0]) * nb, nb)
@@ -278,6 +280,10 @@ class UniBind:
         if pc is not None and pixels is not None:
             pc.pixels = pixels   # of pc.image_embedding, which the call above has stored
         return out
+
+    def choice_constraint(self, choices, eos_token_id=None):
+        """-> the automaton of `generate(constraint=...)` whose paths are exactly `choices` + EOS (`TextModal.choice_constraint`)"""
+        return self.text.choice_constraint(choices, eos_token_id)
 
     def new_prefix_cache(self, kv_cache="bf16", max_positions=None):
         """-> the KV cache of one conversation for `generate(prefix_cache=...)` (generation.PrefixCache, bound to this model's decoder)"""

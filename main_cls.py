@@ -7,7 +7,9 @@ surface (/root/reference main_cls.py:125-220):
 
 build_model -> build_zero_shot_loader(config, mode="zero_shot_cls") -> ONE prompt for the whole run ("[CLS] Choose the best categories
 describe the image from: [class list]" in the default conversation template) repeated over the batch -> greedy `model.generate` ->
-`batch_decode` -> `classname_2_idx` -> balanced accuracy (mean per-class recall) and the per-class report.
+`batch_decode` -> `classname_2_idx` -> balanced accuracy (mean per-class recall) and the per-class report.  With `--opts
+eval.constrained True` the answer is constrained to the class names (`model.choice_constraint`): generation stops behind the name's EOS and
+the automaton's choice is the predicted index.
 
 The loader's workers decode; Resize(256) / CenterCrop(224) / ImageNet normalisation run on the device per batch
 (`lhrs_image_preprocess`); every batch is ONE prefill + one captured hipGraph per generated token for all its rows.
@@ -44,14 +46,24 @@ def main(config):
     tokenizer = model.text.tokenizer
     input_ids = tokenizer_image_token(conv.get_prompt(), tokenizer, IMAGE_TOKEN_INDEX, return_tensors="pt").unsqueeze(0).repeat(int(config.batch_size), 1)
     max_new = 20 if config["eval"]["dataset"] != "METERML" else 30
-    preds, trues = [], []
+    # `--opts eval.constrained True`: the answer is one of the class names (generate(constraint=...)), the prediction the automaton's choice
+    constraint = model.choice_constraint(all_classes) if config["eval"].get("constrained", False) else None
+    preds, trues, choices = [], [], []
     with torch.no_grad():
         for image, target in data_loader:
-            output_ids = model.generate(input_ids=input_ids[: image.shape[0]], images=image, do_sample=False, num_beams=1, temperature=1.0, top_p=1.0,
-                                        max_new_tokens=max_new, weights=generation_weights(config))
+            if constraint is None:
+                output_ids = model.generate(input_ids=input_ids[: image.shape[0]], images=image, do_sample=False, num_beams=1, temperature=1.0, top_p=1.0,
+                                            max_new_tokens=max_new, weights=generation_weights(config))
+            else:
+                output_ids, choice, _ = model.generate(input_ids=input_ids[: image.shape[0]], images=image, do_sample=False, num_beams=1, temperature=1.0,
+                                                       top_p=1.0, max_new_tokens=max_new, weights=generation_weights(config), constraint=constraint,
+                                                       return_choices=True)
+                choices += choice.tolist()
             preds += tokenizer.batch_decode(output_ids, skip_special_tokens=True)
             trues.append(torch.as_tensor(target).cpu())
     pred_idx = classname_2_idx(preds, classes_2_idx)
+    if constraint is not None:   # -1: max_new_tokens ran out inside a class name
+        pred_idx = [c if c >= 0 else p for c, p in zip(choices, pred_idx)]
     trues = torch.cat(trues).tolist()
     score = balanced_accuracy(trues, pred_idx)
     try:
