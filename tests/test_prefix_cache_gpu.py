@@ -283,7 +283,8 @@ def test_rejections_leave_the_cache_usable():
             call()
         now = [t for layer in pc.caches for t in layer]
         assert (pc.ids, pc.length) == state[:2] and pc.image_embedding is state[2] and pc.pixels is state[3], what
-        assert all(torch.equal(a, b) for a, b in zip(now, state[4])), what
+        # bit for bit: the rows past `length` are whatever torch.empty found there, NaN patterns included (NaN != NaN under torch.equal)
+        assert all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(now, state[4])), what
     assert foreign.caches is None and foreign.length == 0
     tok_v, lg_v = m.generate(ids2, images=rgb, **kw)
     assert torch.equal(lg_v, lg) and torch.equal(tok_v, tok)
