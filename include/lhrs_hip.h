@@ -194,6 +194,17 @@ int lhrs_gemm_u4_swiglu_fwd(const void* X, int ldx, const void* Wgu, int ldw, vo
                             void* stream);
 int lhrs_gemm_u4_swiglu_bwd(const void* dY, int ldy, const void* WdT, int ldw, const void* gu, void* dgu, int ld_gu, int M, int ff, int K,
                             void* stream);
+/* The plan of one GEMM call without running it (csrc/gemm_plan.h: the host-only planner every entry point above runs through; pure, no device
+ * work): which kernels the call launches, on which rows, in launch order.  entry: 0 lhrs_gemm_bf16_nt / _lora (K2 > 0) / _dropmask (flag 16),
+ * 1 lhrs_gemm_swiglu_fwd, 2 lhrs_gemm_swiglu_bwd (both: N is taken from ff, ldc from ld_gu), 3 lhrs_gemm_rope_fwd, 4 lhrs_gemm_fp8_nt(_lora),
+ * 5 lhrs_gemm_int8_nt, 6 lhrs_gemm_bf16_nt_splitk_f32.  flags: 1 bias, 2 residual, 4 f32 out, 8 accumulate, 16 dropout mask.  ptr_align: 16 =
+ * every operand pointer is 16-byte aligned (8: only 8-byte).  cus: compute units the rules count rounds in; 0 = the current device's (256 without
+ * a device).  has_workspace: a GEMM workspace of that many 256x256 f32 slabs is registered.  out_quads: cap x (row0, row1, kernel, prof_kind) -
+ * kernel indexes lhrs_gemm_kernel_name(), prof_kind is the kind of lhrs_gemm_profile_read_kinds or -1 (counted, never timed).  A two-launch LoRA
+ * fallback lists its rows twice (base product, then the pair on top).  Returns the number of launches, -1 when rejected. */
+int lhrs_gemm_plan(int entry, int M, int N, int K, int K2, int flags, int act, float alpha, int lda, int ldb, int ldc, int ldr, int ff, int ld_gu,
+                   int ld_act, int rope_cols, int head_dim, int ptr_align, int cus, int has_workspace, int* out_quads, int cap);
+const char* lhrs_gemm_kernel_name(int kernel);
 
 /* ---- LoRA gradients (peft lora.Linear backward; lhrs/models/text_modal.py:133-151) ------------------------- *
  * C[KP,N] (+)= P[M,KP]^T . Q[M,N]: dA = (s dy B)^T x and dB^T = (s x A^T)^T dy straight from token-major operands.  */

@@ -7,7 +7,8 @@
 // HBM; 288 GB makes the second copy free), so dX is NT as well; dW for the projector is NT over transposed
 // activations.  One layout, one kernel family.
 //
-// Kernel family (CDNA4), chosen by tile count in gemm_launch:
+// Kernel family (CDNA4).  Which of them a call launches, on which rows, is decided by the host-only planner gemm_plan.h (the GemmKernel enum names
+// them); the host code at the end of this file validates, plans and runs the plan (gemm_run):
 //   * gemm_nt_256s_kernel<ACT, EPI, K2P> - THE dominant kernel (every LLaMA linear at training batch sizes): 256x256x64 tile, 16 waves (4x4 of
 //     64x64 = 4x4 fragments of v_mfma_f32_16x16x32_bf16 - the dense bf16 shape that costs the least power per FLOP), two 64 KiB LDS stages
 //     filled by direct-to-LDS DMA (global_load_lds_dwordx4, no VGPR round trip), one barrier per stage, PERSISTENT over tiles (one workgroup
@@ -24,6 +25,8 @@
 //   * block id -> tile map is XCD-aware (block b runs on XCD b % 8; each XCD gets a contiguous run of tiles, rastered in groups of 8 tile
 //     rows) so the 32 tiles an XCD works on at a time share 8 A panels and 4 B panels in its L2.
 #include "common.h"
+#include "gemm_plan.h"
+#include "../../include/lhrs_hip.h"
 #include <array>
 #include <map>
 #include <type_traits>
@@ -948,539 +951,10 @@ extern "C" int lhrs_gemm_profile_read_kinds(double* out) {
   return 0;
 }
 
-static int g_gemm_allow_256 = 2;
-// the 16-wave 256x256 kernel walks its tiles PERSISTENTLY: at most one workgroup per CU (128 KiB of LDS each: only one fits anyway),
-// workgroup b takes tiles b, b + grid, ...  0 = one workgroup per tile (kernel A/B tests: lhrs_gemm_set_persistent)
-static int g_gemm_persist = 1;
-extern "C" int lhrs_gemm_set_persistent(int on) { g_gemm_persist = on; return 0; }
-#define LAUNCH_144(ACT_, EPI_, grid_, s_, g_) hipLaunchKernelGGL((gemm_nt_144s_kernel<ACT_, EPI_>), grid_, dim3(768), 0, s_, g_)
-static int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) n = 256;
-    else n = prop.multiProcessorCount;
-  }
-  return n;
-}
-static dim3 grid_256s(long tiles) { return dim3((unsigned)(g_gemm_persist ? (tiles < num_cus() ? tiles : num_cus()) : tiles)); }
-
-// ---- the GEMM workspace -------------------------------------------------------------------------------------------------------------------
-// Caller-owned device memory, registered per device (lhrs_gemm_set_workspace; 64 MiB + 4 KiB for 256 CUs).  One user: the tail rows of a
-// row-split product with a long k-loop are computed split-K through f32 slabs in it (gemm_launch below).  Launches that use it must be ordered on
-// ONE stream per device.  (Round 4 also ran a stream-K tail of the persistent kernel through it: built, correct, slower at every shape of the path -
-// profiles/r04_streamk_ab.txt, DESIGN.md 3.1 - and removed in round 5.)
-static struct { float* slabs; long units; } g_sk[16];
-extern "C" long lhrs_gemm_workspace_bytes() { return 4096 + (long)num_cus() * 256 * 256 * 4; }
-// ws == nullptr: forget the workspace of the current device
-extern "C" int lhrs_gemm_set_workspace(void* ws, long bytes) {
-  int dev = 0;
-  LHRS_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16, "gemm_set_workspace: device %d", dev);
-  if (ws == nullptr) { g_sk[dev].slabs = nullptr; g_sk[dev].units = 0; return 0; }
-  LHRS_REQUIRE(bytes >= lhrs_gemm_workspace_bytes() && ((size_t)ws & 255) == 0, "gemm_set_workspace: %ld bytes (need %ld, 256-B aligned)", bytes,
-               lhrs_gemm_workspace_bytes());
-  g_sk[dev].slabs = (float*)((char*)ws + 4096); g_sk[dev].units = num_cus();
-  return 0;
-}
-// rounds of the P CUs that T tiles of the persistent kernels cost
-static double rounds_256(long T) {
-  const long P = num_cus();
-  return (double)((T + P - 1) / P);
-}
-template <int ACT, int EPI>
-static void launch_256s(GemmArgs& g, hipStream_t s) {
-  const dim3 grid = grid_256s((long)g.tilesM * g.tilesN);
-  if (g.K2 > 0) hipLaunchKernelGGL((gemm_nt_256s_kernel<ACT, EPI, true>), grid, dim3(1024), 0, s, g);
-  else hipLaunchKernelGGL((gemm_nt_256s_kernel<ACT, EPI, false>), grid, dim3(1024), 0, s, g);
-}
-// the 16-wave kernel; a second operand pair (K2 > 0: the fused LoRA product) is a template parameter of it
-#define LAUNCH_256(ACT_, EPI_, grid_, s_, g_) launch_256s<ACT_, EPI_>(g_, s_)
-// Tile height of the persistent kernels: 256 rows (16 waves) or 144 rows (12 waves, gemm_144s_kernel.inc).  Both walk ceil(tiles / CUs) rounds.  A
-// 144-row tile is 0.5625 of the MFMA work of a 256-row tile but costs ~0.8 of its time: more DMA per MFMA (1050 against 1300 TFLOP/s at
-// M = 8190), and a 256-row launch that leaves CUs idle runs its busy CUs at a higher clock (measured at M = 2184, one round each: 73 / 174 / 350
-// / 69 / 191 us against 98 / 205 / 482 / 86 / 225 us for o / down / d-gate|up / d-o / d-qkv).  Take whichever finishes first: at M = 2184 the five
-// N = 4096 products (144 tiles -> 256) go to 144 rows, qkv / gate|up / d-down (432 / 774 / 387 tiles) stay.  0 = never, 1 = cost model, 2 = whenever legal
-static int g_gemm_bm144 = 1;
-static double g_gemm_bm144_cost = 0.8;
-extern "C" int lhrs_gemm_set_bm144(int mode) { g_gemm_bm144 = mode; return 0; }
-static bool pick_144(int M, long tiles_n, int K, int K2, bool drop) {
-  if (g_gemm_bm144 == 0 || K2 > 0 || drop || K < 192) return false;   // the second operand pair (fused LoRA) and the dropout mask live in the 256-row kernel only
-  if (g_gemm_bm144 == 2) return true;
-  const long P = num_cus(), t256 = (long)cdiv(M, 256) * tiles_n, t144 = (long)cdiv(M, 144) * tiles_n;
-  const int nk = K / 64;
-  if (nk <= 32) {
-    // short k-loops (the ViT / projector products, K = 1024 .. 2048): a tile's fixed part - cold first stages, epilogue - weighs as much as
-    // its stages, and it is smaller for the 144-row tile.  Fitted on tools/gemm_vit_sweep.py (us per round: 256 rows 1.5 nk + 20, 144 rows
-    // 1.15 nk + 5): M = 7710: qkv 86.6 -> 68.1 us, o 30.2 -> 25.9; M = 27360: 264.7 -> 214.4, 88.5 -> 69.7; fc1 (496 tiles = 2 rounds) stays
-    return (double)((t144 + P - 1) / P) * (1.15 * nk + 5.0) < (double)((t256 + P - 1) / P) * (1.5 * nk + 20.0);
-  }
-  return (double)((t144 + P - 1) / P) * g_gemm_bm144_cost < rounds_256(t256);
-}
-// fewest 64x128 tiles for which the 64x128 small-tile kernel is taken over the 64x64 one (A/B: lhrs_gemm_set_small_thresh)
-static int g_gemm_small_thresh = 256;
-extern "C" int lhrs_gemm_set_small_thresh(int n) { g_gemm_small_thresh = n; return 0; }
-static int g_gemm_min256 = 128;  // fewest 256x256 tiles (half a round of the 256 CUs) for which the big-tile kernels are chosen: 2184 x 4096 (144
-                                 // tiles, the reference's micro-batch 8) runs 20 % faster there than on 576 small tiles; A/B: lhrs_gemm_set_min_tiles
-extern "C" int lhrs_gemm_set_min_tiles(int n) { g_gemm_min256 = n; return 0; }
-// tile policy switch for A/B measurements: 0 = never a 256x256 / 144x256 persistent kernel (small tiles only), 2 = default
-extern "C" int lhrs_gemm_set_policy(int allow_256) { g_gemm_allow_256 = allow_256 ? 2 : 0; return 0; }
-
-// C ABI ------------------------------------------------------------------------------------------
-static int gemm_launch(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const void* bias,
-                       const void* residual, int ldr, int act, int out_f32, int accumulate, float alpha, const void* A2,
-                       int lda2, const void* B2, int ldb2, int K2, void* stream);
-// epilogue dropout mask of the NEXT gemm_launch on this host thread: set and cleared by lhrs_gemm_bf16_nt_dropmask only (keeps the
-// 21-argument launcher signature out of every other call site); thresh = 0 means no mask
-static thread_local struct { float scale; unsigned seed, thresh; } t_drop = {1.f, 0u, 0u};
-static thread_local bool t_split_ok = true;  // false inside the two launches of a row-split product (see the tail-row rule in gemm_launch)
-static int g_gemm_tail_split = 1;            // kernel A/B tests only (lhrs_gemm_set_tail_split)
-extern "C" int lhrs_gemm_set_tail_split(int on) { g_gemm_tail_split = on; return 0; }
-
-// C = mask * (alpha * A.B^T) / (1 - p) + residual, mask = the counter-based LoRA dropout mask over the [M, N] result (see common.h)
-extern "C" int lhrs_gemm_bf16_nt_dropmask(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
-                                          const void* residual, int ldr, float alpha, float p, unsigned seed, void* stream) {
-  LHRS_REQUIRE(p > 0.f && p < 1.f, "gemm_dropmask: p=%f", p);
-  t_drop.scale = 1.f / (1.f - p); t_drop.seed = seed; t_drop.thresh = (unsigned)((double)p * 4294967296.0);
-  const int rc = gemm_launch(A, lda, B, ldb, C, ldc, M, N, K, nullptr, residual, ldr, 0, 0, 0, alpha, nullptr, 0, nullptr, 0, 0, stream);
-  t_drop.thresh = 0;
-  return rc;
-}
-
-// ---- plain long-k products: the four-wave kernel by a shape rule ------------------------------------------------------------------------
-// A product with a plain epilogue (no bias, no activation, bf16 out, alpha 1; optional bf16 residual) on a long k-loop runs the four-wave
-// gemm_u4_kernel (gemm_u4.hip: 128x128 per wave, paced DMA - 5-18 % faster than the 16-wave kernel on these shapes) whenever its 256x256 tiles
-// fill at least ~80 % of one round of the CUs; everything else takes this file's kernels (gemm_launch).  The rule is a function of the SHAPE only -
-// no timing, no cache, no state: a run is bit-reproducible, every data-parallel rank runs the same kernels, ragged row counts (padded batches,
-// the supervised rows of lm_head) cost nothing, and a capturing stream sees the same kernels as an eager one.  Where the threshold comes from
-// (profiles/r04_plain_first_call_timing.txt, us, 16-wave / four-wave): M = 8190, N = 4096 (512 tiles): K = 4096 204.8 / 196.0, 12288 584.4 / 525.0,
-// 22016 1135.8 / 976.6; M = 3840, N = 4096 (240 tiles): K = 4096 100.9 / 96.8, 22016 560.8 / 476.7; M = 3840, N = 32000: 776.0 / 766.7;
-// M = 4320, N = 1024 (68 tiles): 58.4 / 76.0 - the four-wave kernel has one tile height, so a launch that cannot fill the chip stays on the 144-row /
-// small-tile kernels (M = 2184, N = 4096, the reference's micro-batch 8: 144 tiles).  lhrs_gemm_set_u4(0) / LHRS_GEMM_U4=0: the 16-wave kernels everywhere (kernel A/B tests).
-extern "C" int lhrs_gemm_u4_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const void* residual, int ldr,
-                               void* stream);
-static int g_u4_on = -1;
-static int prof_count(int M, int N, int K, int kind, hipStream_t s);
-static void prof_end(int slot, hipStream_t s);
-static void prof_undo(int slot, int kind, double flops);
-static void plain_env() {
-  if (g_u4_on < 0) {
-    const char* e = getenv("LHRS_GEMM_U4");
-    g_u4_on = (e == nullptr || e[0] != '0') ? 1 : 0;
-  }
-}
-extern "C" int lhrs_gemm_set_u4(int on) { plain_env(); g_u4_on = on ? 1 : 0; return 0; }
-// 1 when lhrs_gemm_bf16_nt runs this problem on gemm_u4_kernel (pure function of the arguments and of lhrs_gemm_set_u4)
-extern "C" int lhrs_gemm_u4_takes(int M, int N, int K, int lda, int ldb, int ldc, int ldr, int has_bias, int act, int out_f32, int accumulate, float alpha) {
-  plain_env();
-  const long tiles = (long)cdiv(M, 256) * cdiv(N, 256);
-  return g_u4_on == 1 && g_gemm_allow_256 != 0 && !has_bias && act == 0 && !out_f32 && !accumulate && alpha == 1.f && K >= 4096 && K % 64 == 0 && M >= 1024 && N >= 1024 &&
-         5 * tiles >= 4L * num_cus() && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && ldr % 8 == 0;
-}
-static int gemm_launch(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const void* bias,
-                       const void* residual, int ldr, int act, int out_f32, int accumulate, float alpha, const void* A2,
-                       int lda2, const void* B2, int ldb2, int K2, void* stream);
-// The fused-epilogue products (qkv + RoPE, gate|up + SwiGLU, d-down + SwiGLU') on the four-wave kernel: a LoRA pair in the k-loop only for RoPE (stage 3's
-// q|k|v adapters; the SwiGLU products with a pair live in the 16-wave kernel), K >= 4096, and a tile walk whose rounds leave at most 15 % (SwiGLU backward: 5 %) of the CU-rounds idle (idle share over ALL rounds, R / T <= 1.15) - the four-wave kernel has one tile height and no tail-row
-// split for the fused epilogues.  RoPE and SwiGLU forward: 15 % (micro-batch 30: 6.0 / 10.75 rounds, micro-batch 60: 12 / 21.5: taken; the reference's micro-batch 8,
-// M = 2184: 1.69 / 3.02 rounds: the 16-wave kernels with their 144-row tiles and tail-row rules).  SwiGLU backward: 5 % - its write-out is VALU-bound on four waves
-// (the sigmoid of 256 elements per lane beside one stage of MFMAs), so it only wins where the tile walk fits: micro-batch 60 (10.75 rounds) 1261 us against the 16-wave
-// kernel's ~1307; micro-batch 30 (5.375 rounds) 678 against 634 on the same box (profiles/r05_bench_line_b30_ab_16wave.json) - stays on the 16-wave kernel.
-// kind: 0 RoPE (tiles_n = N / 256), 1 SwiGLU forward (ff / 128), 2 SwiGLU backward (ff / 256).  A pure function of the shape.
-extern "C" int lhrs_gemm_u4_fused_takes(int kind, int M, int tiles_n, int K, int K2) {
-  plain_env();
-  const long P = num_cus(), T = (long)cdiv(M, 256) * tiles_n, R = (T + P - 1) / P * P;
-  const long idle_ok = kind == 2 ? 100 * R <= 105 * T : 20 * R <= 23 * T;
-  return g_u4_on == 1 && g_gemm_allow_256 != 0 && (kind == 0 ? K2 % 64 == 0 : K2 == 0) && K >= 4096 && K % 64 == 0 && M >= 1024 && 5 * T >= 4 * P && idle_ok;
-}
-extern "C" int lhrs_gemm_u4_rope(const void* X, int ldx, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const float* cos_t, const float* sin_t,
-                                 int pos_mod, int pos0, int rope_cols, void* stream);
-extern "C" int lhrs_gemm_u4_rope_lora(const void* X, int ldx, const void* W, int ldw, const void* A2, int lda2, const void* B2, int ldb2, int K2, void* C, int ldc,
-                                      int M, int N, int K, const float* cos_t, const float* sin_t, int pos_mod, int pos0, int rope_cols, void* stream);
-extern "C" int lhrs_gemm_u4_nt_lora(const void* A, int lda, const void* B, int ldb, const void* A2, int lda2, const void* B2, int ldb2, int K2, void* C, int ldc,
-                                    int M, int N, int K, const void* residual, int ldr, void* stream);
-extern "C" int lhrs_gemm_u4_swiglu_fwd(const void* X, int ldx, const void* Wgu, int ldw, void* gu, int ld_gu, void* act, int ld_act, int M, int ff, int K, void* stream);
-extern "C" int lhrs_gemm_u4_swiglu_bwd(const void* dY, int ldy, const void* WdT, int ldw, const void* gu, void* dgu, int ld_gu, int M, int ff, int K, void* stream);
-#define U4_FUSED_TRY(kind_, flopsN_, call_)                                                                          \
-  {                                                                                                                  \
-    const int pslot_ = prof_count(M, flopsN_, K, kind_, (hipStream_t)stream);                                        \
-    const int st_ = call_;                                                                                           \
-    if (st_ == 0) { prof_end(pslot_, (hipStream_t)stream); return 0; }                                               \
-    if (st_ < 0) return st_;                                                                                         \
-    prof_undo(pslot_, kind_, 2.0 * M * (double)(flopsN_) * K);   /* declined (addressing limits): as if never counted */ \
-  }
-
-static int tail_rows_splitk(const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C, int ldc, int M_tail, int N, int K, const bf16_t* residual, int ldr,
-                            float alpha, hipStream_t s);
-// The four-wave kernel walks whole 256x256 tiles in ceil(T / P) rounds of the P CUs.  When the last round would be mostly empty (M = 8736, BASELINE configs[3]'s
-// micro-batch 32: 35 x 16 = 560 tiles = 2.19 rounds -> 3) the rows are cut behind the last tile row the whole rounds cover: those rows go to gemm_u4_kernel, the
-// remaining rows (544 of 8736) to gemm_launch's kernels (small tiles, split-K over the workspace for the long k-loops) - disjoint rows of C.  Returns the number of
-// rows for gemm_u4_kernel (M itself: no cut).  A pure function of the shape.
-static int u4_main_rows(int M, long tiles_n) {
-  const long P = num_cus(), tm = cdiv(M, 256), T = tm * tiles_n, full = T / P;
-  if (T % P == 0 || full < 1 || 20 * ((T + P - 1) / P * P) <= 23 * T) return M;        // whole rounds, or the idle share of the last round is <= 15 %
-  const long tm_main = full * P / tiles_n;
-  return tm_main >= 1 && tm_main < tm ? (int)(tm_main * 256) : M;
-}
-extern "C" int lhrs_gemm_u4_main_rows(int M, int N) { return u4_main_rows(M, cdiv(N, 256)); }
-
-// the plain-epilogue product on gemm_u4_kernel when the shape rule takes it (optionally with the LoRA pair in the k-loop): 0 done, 1 not taken, -1 error
-static int plain_u4_try(const void* A, int lda, const void* B, int ldb, const void* A2, int lda2, const void* B2, int ldb2, int K2, void* C, int ldc, int M, int N,
-                        int K, const void* bias, const void* residual, int ldr, int act, int out_f32, int accumulate, float alpha, void* stream) {
-  if (!lhrs_gemm_u4_takes(M, N, K, lda, ldb, ldc, residual ? ldr : 0, bias != nullptr, act, out_f32, accumulate, alpha) || t_drop.thresh != 0 ||
-      ((size_t)A | (size_t)B | (size_t)C | (size_t)residual | (size_t)A2 | (size_t)B2) % 16 != 0)
-    return 1;
-  hipStream_t s = (hipStream_t)stream;
-  const int Mu = u4_main_rows(M, cdiv(N, 256));
-  const int ukind = residual ? 5 : 6;
-  const int slot = prof_count(Mu, N, K + K2, ukind, s);
-  const int st = K2 > 0 ? lhrs_gemm_u4_nt_lora(A, lda, B, ldb, A2, lda2, B2, ldb2, K2, C, ldc, Mu, N, K, residual, ldr, stream)
-                        : lhrs_gemm_u4_nt(A, lda, B, ldb, C, ldc, Mu, N, K, residual, ldr, stream);
-  if (st == 0) {
-    prof_end(slot, s);
-    if (Mu == M) return 0;
-    const bf16_t* At = (const bf16_t*)A + (long)Mu * lda;
-    const bf16_t* Rt = residual ? (const bf16_t*)residual + (long)Mu * ldr : nullptr;
-    bf16_t* Ct = (bf16_t*)C + (long)Mu * ldc;
-    if (K2 == 0) {   // the split-K tail has no second operand pair: a product with one takes the small-tile kernels over its whole k-loop
-      const int ts = tail_rows_splitk(At, lda, (const bf16_t*)B, ldb, Ct, ldc, M - Mu, N, K, Rt, ldr, 1.f, s);
-      if (ts <= 0) return ts;
-    }
-    return gemm_launch(At, lda, B, ldb, Ct, ldc, M - Mu, N, K, nullptr, Rt, ldr, 0, 0, 0, 1.f, K2 > 0 ? (const bf16_t*)A2 + (long)Mu * lda2 : nullptr, lda2, B2, ldb2,
-                       K2, stream) ? -1 : 0;
-  }
-  if (st < 0) return st;
-  prof_undo(slot, ukind, 2.0 * Mu * N * (K + K2));   // not its problem after all (addressing limits): as if never counted
-  return 1;
-}
-
-extern "C" int lhrs_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N,
-                                 int K, const void* bias, const void* residual, int ldr, int act, int out_f32,
-                                 int accumulate, float alpha, void* stream) {
-  const int st = plain_u4_try(A, lda, B, ldb, nullptr, 0, nullptr, 0, 0, C, ldc, M, N, K, bias, residual, ldr, act, out_f32, accumulate, alpha, stream);
-  if (st <= 0) return st;
-  return gemm_launch(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, act, out_f32, accumulate, alpha, nullptr, 0, nullptr, 0,
-                     0, stream);
-}
-
-// C = alpha * (A.B^T + A2.B2^T) + bias + residual: the rank-K2 LoRA update rides in the k-loop of the base GEMM
-// (peft lora.Linear forward, y = W x + (alpha/r) B A x, reached from lhrs/models/text_modal.py:133-151).  The same shape rule as lhrs_gemm_bf16_nt decides
-// between gemm_u4_kernel and the 16-wave kernels (the pair adds K2 / 64 stages to either k-loop; the two are bit-identical).
-extern "C" int lhrs_gemm_bf16_nt_lora(const void* A, int lda, const void* B, int ldb, const void* A2, int lda2, const void* B2,
-                                      int ldb2, int K2, void* C, int ldc, int M, int N, int K, const void* bias,
-                                      const void* residual, int ldr, int out_f32, int accumulate, float alpha, void* stream) {
-  LHRS_REQUIRE(A2 && B2 && K2 > 0 && K2 % 64 == 0 && lda2 % 8 == 0 && ldb2 % 8 == 0 && lda2 >= K2 && ldb2 >= K2,
-               "gemm_lora: bad second operand pair (K2=%d lda2=%d ldb2=%d)", K2, lda2, ldb2);
-  const int st = plain_u4_try(A, lda, B, ldb, A2, lda2, B2, ldb2, K2, C, ldc, M, N, K, bias, residual, ldr, 0, out_f32, accumulate, alpha, stream);
-  if (st <= 0) return st;
-  return gemm_launch(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, 0, out_f32, accumulate, alpha, A2, lda2, B2, ldb2, K2,
-                     stream);
-}
-
-// The tail rows of a row-split product with a LONG k-loop (M = 8736: 544 rows x 4096 columns = 160 tiles of 128^2, each walking K = 11008 .. 22016 alone: 100 - 190
-// us at 500 TFLOP/s, tools/gemm_tail_sweep.py): K is cut into slabs of ~4096 across blockIdx.y - f32 slabs in the registered workspace, summed in a fixed order with
-// the residual by one small launch - so that every CU has work for the whole tail.  0 launched, 1 not applicable (short k-loop, no workspace), -1 error.
-static int tail_rows_splitk(const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C, int ldc, int M_tail, int N, int K, const bf16_t* residual, int ldr,
-                            float alpha, hipStream_t s) {
-  int dev = 0;
-  const int splits = K >= 8192 ? (K + 2048) / 4096 : 1;
-  if (splits <= 1 || N % 128 != 0 || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16 || g_sk[dev].slabs == nullptr ||
-      (long)splits * M_tail * N * 4 > g_sk[dev].units * 256 * 256 * 4)
-    return 1;
-  const int ks = cdiv(K / 64, splits) * 64, used = cdiv(K, ks);
-  GemmArgs gt; memset(&gt, 0, sizeof(gt));
-  gt.A = A; gt.B = B; gt.C = g_sk[dev].slabs; gt.M = M_tail; gt.N = N; gt.K = K;
-  gt.lda = lda; gt.ldb = ldb; gt.ldc = N; gt.alpha = 1.f; gt.out_f32 = 1; gt.ksplit = ks; gt.drop_scale = 1.f;
-  gt.tilesM = cdiv(M_tail, 128); gt.tilesN = cdiv(N, 128);
-  if (g_prof.on) { g_prof.launches_all++; g_prof.total_flops_all += 2.0 * M_tail * N * K; }
-  hipLaunchKernelGGL((gemm_nt_kernel<4, 4, 0>), dim3(gt.tilesM * gt.tilesN, used), dim3(256), 0, s, gt);
-  const long work = (long)M_tail * (N / 4);
-  int rg = (int)((work + 255) / 256); if (rg > 8192) rg = 8192;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rg), dim3(256), 0, s, (const float*)g_sk[dev].slabs, C, (long)ldc, M_tail, N, used, alpha, residual, (long)ldr);
-  LHRS_CHECK_LAUNCH("gemm_tail_splitk");
-  return 0;
-}
-
-static int gemm_launch(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const void* bias,
-                       const void* residual, int ldr, int act, int out_f32, int accumulate, float alpha, const void* A2,
-                       int lda2, const void* B2, int ldb2, int K2, void* stream) {
-  LHRS_REQUIRE(M > 0 && N > 0 && K > 0, "gemm: empty problem M=%d N=%d K=%d", M, N, K);
-  LHRS_REQUIRE(K % 64 == 0, "gemm: K=%d must be a multiple of 64 (zero-pad the reduction dim)", K);
-  LHRS_REQUIRE(N % 4 == 0, "gemm: N=%d must be a multiple of 4", N);
-  LHRS_REQUIRE(lda % 8 == 0 && ldb % 8 == 0, "gemm: lda=%d ldb=%d must be multiples of 8 (16-B rows)", lda, ldb);
-  LHRS_REQUIRE(ldc % 4 == 0 && (residual == nullptr || ldr % 4 == 0), "gemm: ldc/ldr must be multiples of 4");
-  LHRS_REQUIRE(lda >= K && ldb >= K && ldc >= N, "gemm: leading dims too small");
-  LHRS_REQUIRE(!accumulate || out_f32, "gemm: accumulate needs f32 output");
-  LHRS_REQUIRE(act >= 0 && act <= 3, "gemm: unknown activation %d", act);
-  GemmArgs g;
-  g.epi = 0; g.ff = 0; g.aux = nullptr; g.aux_out = nullptr; g.ld_aux = 0; g.sa = nullptr; g.sb = nullptr; g.ksplit = 0; g.drop_scale = 1.f; g.drop_seed = 0; g.drop_thresh = 0;
-  g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = C;
-  g.bias = (const bf16_t*)bias; g.res = (const bf16_t*)residual;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr;
-  g.alpha = alpha; g.act = act; g.out_f32 = out_f32; g.accum = accumulate;
-  g.A2 = (const bf16_t*)A2; g.B2 = (const bf16_t*)B2; g.lda2 = lda2; g.ldb2 = ldb2; g.K2 = K2;
-  g.drop_scale = t_drop.scale; g.drop_seed = t_drop.seed; g.drop_thresh = t_drop.thresh;
-  hipStream_t s = (hipStream_t)stream;
-  // Tile choice: fill the 256 CUs.  Small problems (projector, ViT at small batch) take smaller tiles.
-  const long t128 = (long)cdiv(M, 128) * cdiv(N, 128);
-  const long t64x128 = (long)cdiv(M, 64) * cdiv(N, 128);
-#define LAUNCH_TILE(WM, WN)                                                                            \
-  do {                                                                                                 \
-    g.tilesM = cdiv(M, WM * 32); g.tilesN = cdiv(N, WN * 32);                                          \
-    const dim3 grid(g.tilesM * g.tilesN), blk(256);                                                    \
-    switch (act) {                                                                                     \
-      case 0: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, 0>), grid, blk, 0, s, g); break;              \
-      case 1: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, 1>), grid, blk, 0, s, g); break;              \
-      case 2: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, 2>), grid, blk, 0, s, g); break;              \
-      default: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, 3>), grid, blk, 0, s, g); break;             \
-    }                                                                                                  \
-  } while (0)
-  const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
-  const bool al16 = out_f32 || (N % 8 == 0 && ldc % 8 == 0 && (residual == nullptr || ldr % 8 == 0));  // 16-B epilogue rows
-  bool use256 = g_gemm_allow_256 && t256 >= g_gemm_min256 && K >= 128 && al16;  // the persistent kernels' pipeline needs >= 2 stages
-  // just under the big-tile threshold but nearly a full round of 144-row tiles (ViT o / fc2 at micro-batch 30: 124 tiles of 256 rows, 216 of
-  // 144): the persistent 144-row kernel beats the small tiles (30.2 -> 25.9, 75.1 -> 68.4 us; tools/gemm_vit_sweep.py)
-  if (!use256 && g_gemm_allow_256 == 2 && g_gemm_bm144 == 1 && al16 && !out_f32 && K % 64 == 0 && K >= 192 && K2 == 0 && !g.drop_thresh &&
-      t256 >= g_gemm_min256 / 2 && (long)cdiv(M, 144) * cdiv(N, 256) >= 200 && (long)cdiv(M, 144) * cdiv(N, 256) <= num_cus())
-    use256 = true;
-  if (K2 > 0 && !use256) {  // small problems: base GEMM, then the rank-K2 update accumulated on top of it
-    if (gemm_launch(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, act, out_f32, accumulate, alpha, nullptr, 0, nullptr, 0, 0, stream))
-      return -1;
-    return gemm_launch(A2, lda2, B2, ldb2, C, ldc, M, N, K2, nullptr, out_f32 ? nullptr : C, ldc, 0, out_f32, out_f32 ? 1 : 0, alpha,
-                       nullptr, 0, nullptr, 0, 0, stream);
-  }
-  // Tail rows: T = tilesM * tilesN 256x256 tiles run as ceil(T / 256) rounds of the 256 CUs, and a nearly empty last round costs as
-  // much as a full one (M = 8736, N = 4096: 560 tiles = 2.19 rounds -> 3).  When the tile rows that spill over the last full round
-  // are cheaper as a separate small-tile launch (~2.5x the time per FLOP, but no idle CUs), the row range is cut there: whole
-  // 256-row tile rows for the 16-wave kernel, the remaining rows for the 64x128 / 128x128 kernel.  Disjoint rows of C, no partials.
-  const bool s_kernel = use256;
-  const bool bm144 = s_kernel && !out_f32 && pick_144(M, cdiv(N, 256), K, K2, g.drop_thresh != 0);
-  if (s_kernel && !bm144 && t_split_ok && g_gemm_tail_split && !g.drop_thresh) {
-    const int tm = cdiv(M, 256), tn = cdiv(N, 256);
-    const long T = (long)tm * tn, rounds = (T + 255) / 256, full = T / 256;
-    const int tm_main = (int)(full * 256 / tn);
-    if (full >= 1 && T % 256 != 0 && tm_main >= 1 && tm_main < tm) {
-      const long t_main = (long)tm_main * tn, t_tail = T - t_main;
-      const double split_cost = (double)((t_main + 255) / 256) + 2.5 * (double)t_tail / 256.0 + 0.05;
-      (void)rounds;
-      if (split_cost < rounds_256(T)) {
-        const int M_main = tm_main * 256, M_tail = M - M_main;
-        const long esz = out_f32 ? 4 : 2;
-        t_split_ok = false;
-        int rc = gemm_launch(A, lda, B, ldb, C, ldc, M_main, N, K, bias, residual, ldr, act, out_f32, accumulate, alpha, A2, lda2, B2, ldb2, K2, stream);
-        if (!rc && !out_f32 && K2 == 0 && bias == nullptr && act == 0) {
-          const int ts = tail_rows_splitk((const bf16_t*)A + (long)M_main * lda, lda, (const bf16_t*)B, ldb, (bf16_t*)C + (long)M_main * ldc, ldc, M_tail, N, K,
-                                          residual ? (const bf16_t*)residual + (long)M_main * ldr : nullptr, ldr, alpha, s);
-          if (ts <= 0) { t_split_ok = true; return ts; }
-        }
-        if (!rc)
-          rc = gemm_launch((const bf16_t*)A + (long)M_main * lda, lda, B, ldb, (char*)C + (long)M_main * ldc * esz, ldc, M_tail, N, K, bias,
-                           residual ? (const bf16_t*)residual + (long)M_main * ldr : nullptr, ldr, act, out_f32, accumulate, alpha,
-                           A2 ? (const bf16_t*)A2 + (long)M_main * lda2 : nullptr, lda2, B2, ldb2, K2, stream);
-        t_split_ok = true;
-        return rc;
-      }
-    }
-  }
-  const bool big = t128 >= 384;
-  int slot = -1;
-  if (g_prof.on) {
-    g_prof.launches_all++; g_prof.total_flops_all += 2.0 * M * N * (K + K2);
-    const bool dominant = s_kernel;
-    const int pkind = bm144 ? 4 : 0;
-    if (dominant && g_prof.used < g_prof.cap && g_prof.take(pkind)) {  // time the launches rocprof lists as gemm_nt_256s_kernel<ACT, 0 ...> (kind 0) / gemm_nt_144s_kernel<ACT, 0> (kind 4)
-      slot = g_prof.used++;
-      g_prof.flops[slot] = 2.0 * M * N * (K + K2);
-      g_prof.kind[slot] = pkind;
-      (void)hipEventRecord(g_prof.ev[2 * slot], s);
-    }
-  }
-  if (use256) {
-    g.tilesM = cdiv(M, 256); g.tilesN = cdiv(N, 256);
-    if (bm144) {
-      g.tilesM = cdiv(M, 144);
-      const dim3 grid12 = grid_256s((long)g.tilesM * g.tilesN);
-      switch (act) {
-        case 0: LAUNCH_144(0, 0, grid12, s, g); break;
-        case 1: LAUNCH_144(1, 0, grid12, s, g); break;
-        case 2: LAUNCH_144(2, 0, grid12, s, g); break;
-        default: LAUNCH_144(3, 0, grid12, s, g); break;
-      }
-    } else {
-      const dim3 grid16 = grid_256s((long)g.tilesM * g.tilesN);
-      switch (act) {
-        case 0: LAUNCH_256(0, 0, grid16, s, g); break;
-        case 1: LAUNCH_256(1, 0, grid16, s, g); break;
-        case 2: LAUNCH_256(2, 0, grid16, s, g); break;
-        default: LAUNCH_256(3, 0, grid16, s, g); break;
-      }
-    }
-  } else if (big) LAUNCH_TILE(4, 4);
-  else if (t64x128 >= g_gemm_small_thresh) LAUNCH_TILE(2, 4);
-  else LAUNCH_TILE(2, 2);
-#undef LAUNCH_TILE
-  if (slot >= 0) (void)hipEventRecord(g_prof.ev[2 * slot + 1], s);
-  LHRS_CHECK_LAUNCH("gemm_bf16_nt");
-  return 0;
-}
-
-
-// ---- LLaMA MLP with the SwiGLU fused into the GEMM epilogues (HF LlamaMLP, reached from lhrs/models/text_modal.py:258-294) ----------
-// forward : gu[M, 2*ff] = x W_gu^T (+ LoRA pair), act[M, ff] = silu(gu[:, :ff]) * gu[:, ff:]     - one launch instead of GEMM + swiglu_fwd
-// backward: dgu[M, 2*ff] = swiglu'(gu) * (dy W_down) (+ LoRA pair); dgu may alias gu             - one launch instead of GEMM + swiglu_bwd
-// Results are bit-identical to the unfused sequence (the epilogue rounds gate / up / d_act to bf16 exactly where the unfused path
-// stores them).  Shapes the 16-wave 256x256 kernel does not take (K % 64, fewer tiles than the big-tile threshold, ff % 128) fall back to the unfused sequence.
-extern "C" int lhrs_swiglu_fwd(const void* gate_up, void* act, long rows, int F, void* stream);
-extern "C" int lhrs_swiglu_bwd(const void* dact, const void* gate_up, void* dgate_up, long rows, int F, void* stream);
-extern "C" int lhrs_rope(void* x, long ld, int rows, int nheads, int D, const float* cos_t, const float* sin_t, const int* pos_ids, int pos_mod,
-                         int pos0, int inverse, void* stream);
-
-static bool swiglu_fusable(long tiles, int ff, int K, int K2, int lda, int ldb) {
-  return g_gemm_allow_256 == 2 && ff % 256 == 0 && K % 64 == 0 && K2 % 64 == 0 && K + K2 >= 128 && tiles >= g_gemm_min256 &&
-         lda % 8 == 0 && ldb % 8 == 0;
-}
-// 1 when lhrs_gemm_swiglu_fwd / _bwd will take the fused kernel for this problem (dense operands), else 0 (they fall back)
-extern "C" int lhrs_gemm_swiglu_fusable(int M, int ff, int K_fwd, int K_bwd, int K2) {
-  const long tf = (long)cdiv(M, 256) * (ff / 128), tb = (long)cdiv(M, 256) * cdiv(ff, 256);
-  return swiglu_fusable(tf, ff, K_fwd, K2, 8, 8) && swiglu_fusable(tb, ff, K_bwd, K2, 8, 8);
-}
-
-// the fused-epilogue launches count towards the step's GEMM FLOPs but are NOT timed as "the dominant kernel": their epilogues do
-// elementwise work (SwiGLU) that has no FLOPs in the GEMM roofline - the live roofline figure is the plain gemm_nt_256s_kernel<ACT, 0, K2P>
-static int prof_count(int M, int N, int K, int kind, hipStream_t s) {
-  if (!g_prof.on) return -1;
-  g_prof.launches_all++; g_prof.total_flops_all += 2.0 * M * N * K;
-  if (g_prof.used >= g_prof.cap || !g_prof.take(kind)) return -1;
-  const int slot = g_prof.used++;
-  g_prof.flops[slot] = 2.0 * M * N * K; g_prof.kind[slot] = kind;
-  (void)hipEventRecord(g_prof.ev[2 * slot], s);
-  return slot;
-}
-static void prof_end(int slot, hipStream_t s) {
-  if (slot >= 0) (void)hipEventRecord(g_prof.ev[2 * slot + 1], s);
-}
-// a launch prof_count counted was declined by its kernel wrapper: everything prof_count did is taken back - the slot (the last one handed out), the totals, and the
-// sampling phase seen[kind], which take() advanced exactly when a slot was free (whether or not this launch was the stride's sample)
-static void prof_undo(int slot, int kind, double flops) {
-  if (!g_prof.on) return;
-  g_prof.launches_all--; g_prof.total_flops_all -= flops;
-  if (slot >= 0) g_prof.used--;
-  if (slot >= 0 || g_prof.used < g_prof.cap) g_prof.seen[kind]--;
-}
-
-extern "C" int lhrs_gemm_swiglu_fwd(const void* X, int ldx, const void* Wgu, int ldw, const void* A2, int lda2, const void* B2, int ldb2,
-                                    int K2, void* gu, int ld_gu, void* act, int ld_act, int M, int ff, int K, void* stream) {
-  LHRS_REQUIRE(M > 0 && ff > 0 && K > 0 && ff % 8 == 0 && ld_gu >= 2 * ff && ld_act >= ff && ld_gu % 8 == 0 && ld_act % 8 == 0,
-               "gemm_swiglu_fwd: M=%d ff=%d K=%d ld_gu=%d ld_act=%d", M, ff, K, ld_gu, ld_act);
-  if (ff % 128 == 0 && lhrs_gemm_u4_fused_takes(1, M, ff / 128, K, K2))
-    U4_FUSED_TRY(7, 2 * ff, lhrs_gemm_u4_swiglu_fwd(X, ldx, Wgu, ldw, gu, ld_gu, act, ld_act, M, ff, K, stream))
-  if (!swiglu_fusable((long)cdiv(M, 256) * (ff / 128), ff, K, K2, ldx, ldw)) {
-    if (gemm_launch(X, ldx, Wgu, ldw, gu, ld_gu, M, 2 * ff, K, nullptr, nullptr, 0, 0, 0, 0, 1.f, A2, lda2, B2, ldb2, K2, stream)) return -1;
-    LHRS_REQUIRE(ld_gu == 2 * ff && ld_act == ff, "gemm_swiglu_fwd: the unfused fallback needs dense gu / act");
-    return lhrs_swiglu_fwd(gu, act, M, ff, stream);
-  }
-  // Tail rows, as in gemm_launch: when the tile rows that spill over the last full round of the 256 CUs are cheaper as a small-tile launch
-  // (M = 2184, the reference's micro-batch 8: 9 x 86 = 774 tiles = 3 rounds + SIX tiles), the fused kernel takes the whole tile rows and the
-  // remaining rows go through the plain GEMM + the SwiGLU kernel - the same bf16 gate|up rows, the same silu(gate) * up on them
-  const bool bm144 = pick_144(M, ff / 128, K, K2, false);
-  if (!bm144 && t_split_ok && g_gemm_tail_split && ld_gu == 2 * ff && ld_act == ff) {
-    const int tm = cdiv(M, 256), tn = ff / 128;
-    const long T = (long)tm * tn, rounds = (T + 255) / 256, full = T / 256;
-    const int tm_main = (int)(full * 256 / tn);
-    if (full >= 1 && T % 256 != 0 && tm_main >= 1 && tm_main < tm) {
-      const long t_main = (long)tm_main * tn, t_tail = T - t_main;
-      if ((double)((t_main + 255) / 256) + 2.5 * (double)t_tail / 256.0 + 0.05 < (double)rounds) {
-        const int M_main = tm_main * 256, M_tail = M - M_main;
-        t_split_ok = false;
-        int rc = lhrs_gemm_swiglu_fwd(X, ldx, Wgu, ldw, A2, lda2, B2, ldb2, K2, gu, ld_gu, act, ld_act, M_main, ff, K, stream);
-        t_split_ok = true;
-        if (rc) return rc;
-        bf16_t* gu_t = (bf16_t*)gu + (long)M_main * ld_gu;
-        if (gemm_launch((const bf16_t*)X + (long)M_main * ldx, ldx, Wgu, ldw, gu_t, ld_gu, M_tail, 2 * ff, K, nullptr, nullptr, 0, 0, 0, 0, 1.f,
-                        A2 ? (const bf16_t*)A2 + (long)M_main * lda2 : nullptr, lda2, B2, ldb2, K2, stream))
-          return -1;
-        return lhrs_swiglu_fwd(gu_t, (bf16_t*)act + (long)M_main * ld_act, M_tail, ff, stream);
-      }
-    }
-  }
-  GemmArgs g; memset(&g, 0, sizeof(g));
-  g.A = (const bf16_t*)X; g.B = (const bf16_t*)Wgu; g.C = gu; g.M = M; g.N = 2 * ff; g.K = K; g.lda = ldx; g.ldb = ldw; g.ldc = ld_gu;
-  g.alpha = 1.f; g.A2 = (const bf16_t*)A2; g.B2 = (const bf16_t*)B2; g.lda2 = lda2; g.ldb2 = ldb2; g.K2 = K2;
-  g.epi = 1; g.ff = ff; g.aux_out = (bf16_t*)act; g.ld_aux = ld_act;
-  g.tilesM = cdiv(M, bm144 ? 144 : 256); g.tilesN = ff / 128;
-  hipStream_t s = (hipStream_t)stream;
-  const int pslot = prof_count(M, 2 * ff, K + K2, 1, s);
-  if (bm144) LAUNCH_144(0, 1, grid_256s((long)g.tilesM * g.tilesN), s, g);
-  else LAUNCH_256(0, 1, grid_256s((long)g.tilesM * g.tilesN), s, g);
-  prof_end(pslot, s);
-  LHRS_CHECK_LAUNCH("gemm_swiglu_fwd");
-  return 0;
-}
-
-// qkv = x . Wqkv^T (+ fused LoRA pair) with the RoPE of the q / k heads (HF apply_rotary_pos_emb, rotate_half convention, head_dim 128)
-// applied in the GEMM epilogue: columns [0, rope_cols) are heads of 128 that get rotated with the position m % pos_mod + pos0 of
-// their row, the remaining columns (v) are stored as computed.  Bit-identical to lhrs_gemm_bf16_nt(_lora) followed by lhrs_rope; that
-// pair is also the fallback when the 256-tile kernel does not apply.
-extern "C" int lhrs_gemm_rope_fwd(const void* X, int ldx, const void* W, int ldw, const void* A2, int lda2, const void* B2, int ldb2, int K2,
-                                  void* C, int ldc, int M, int N, int K, const float* cos_t, const float* sin_t, int pos_mod, int pos0,
-                                  int rope_cols, int head_dim, void* stream) {
-  LHRS_REQUIRE(M > 0 && N > 0 && K > 0 && head_dim % 16 == 0 && rope_cols >= 0 && rope_cols <= N && rope_cols % head_dim == 0 && pos_mod > 0 &&
-                   cos_t && sin_t && ldc % 8 == 0,
-               "gemm_rope_fwd: M=%d N=%d K=%d rope_cols=%d head_dim=%d pos_mod=%d", M, N, K, rope_cols, head_dim, pos_mod);
-  const long tiles = (long)cdiv(M, 256) * cdiv(N, 256);
-  const bool fused = g_gemm_allow_256 == 2 && head_dim == 128 && rope_cols % 256 == 0 && N % 8 == 0 && K % 64 == 0 &&
-                     K2 % 64 == 0 && K + K2 >= 128 && tiles >= g_gemm_min256 && ldx % 8 == 0 && ldw % 8 == 0;
-  if (!fused) {
-    if (gemm_launch(X, ldx, W, ldw, C, ldc, M, N, K, nullptr, nullptr, 0, 0, 0, 0, 1.f, A2, lda2, B2, ldb2, K2, stream)) return -1;
-    if (rope_cols == 0) return 0;
-    return lhrs_rope(C, ldc, M, rope_cols / head_dim, head_dim, cos_t, sin_t, nullptr, pos_mod, pos0, 0, stream);
-  }
-  if (head_dim == 128 && rope_cols % 256 == 0 && lhrs_gemm_u4_fused_takes(0, M, cdiv(N, 256), K, K2))
-    U4_FUSED_TRY(9, N, K2 > 0 ? lhrs_gemm_u4_rope_lora(X, ldx, W, ldw, A2, lda2, B2, ldb2, K2, C, ldc, M, N, K, cos_t, sin_t, pos_mod, pos0, rope_cols, stream)
-                              : lhrs_gemm_u4_rope(X, ldx, W, ldw, C, ldc, M, N, K, cos_t, sin_t, pos_mod, pos0, rope_cols, stream))
-  GemmArgs g; memset(&g, 0, sizeof(g));
-  g.A = (const bf16_t*)X; g.B = (const bf16_t*)W; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldb = ldw; g.ldc = ldc;
-  g.alpha = 1.f; g.A2 = (const bf16_t*)A2; g.B2 = (const bf16_t*)B2; g.lda2 = lda2; g.ldb2 = ldb2; g.K2 = K2;
-  g.epi = 3; g.rope_cos = cos_t; g.rope_sin = sin_t; g.rope_mod = pos_mod; g.rope_pos0 = pos0; g.rope_cols = rope_cols;
-  const bool bm144 = pick_144(M, cdiv(N, 256), K, K2, false);
-  g.tilesM = cdiv(M, bm144 ? 144 : 256); g.tilesN = cdiv(N, 256);
-  const int pslot = prof_count(M, N, K + K2, 3, (hipStream_t)stream);
-  if (bm144) LAUNCH_144(0, 3, grid_256s((long)g.tilesM * g.tilesN), (hipStream_t)stream, g);
-  else LAUNCH_256(0, 3, grid_256s((long)g.tilesM * g.tilesN), (hipStream_t)stream, g);
-  prof_end(pslot, (hipStream_t)stream);
-  LHRS_CHECK_LAUNCH("gemm_rope_fwd");
-  return 0;
-}
-
-extern "C" int lhrs_gemm_swiglu_bwd(const void* dY, int ldy, const void* WdT, int ldw, const void* A2, int lda2, const void* B2, int ldb2,
-                                    int K2, const void* gu, void* dgu, int ld_gu, void* dact_scratch, int M, int ff, int K, void* stream) {
-  LHRS_REQUIRE(M > 0 && ff > 0 && K > 0 && ff % 8 == 0 && ld_gu >= 2 * ff && ld_gu % 8 == 0, "gemm_swiglu_bwd: M=%d ff=%d K=%d ld_gu=%d", M, ff, K, ld_gu);
-  if (lhrs_gemm_u4_fused_takes(2, M, cdiv(ff, 256), K, K2))
-    U4_FUSED_TRY(8, ff, lhrs_gemm_u4_swiglu_bwd(dY, ldy, WdT, ldw, gu, dgu, ld_gu, M, ff, K, stream))
-  if (!swiglu_fusable((long)cdiv(M, 256) * cdiv(ff, 256), ff, K, K2, ldy, ldw)) {
-    LHRS_REQUIRE(dact_scratch != nullptr && ld_gu == 2 * ff, "gemm_swiglu_bwd: the unfused fallback needs a [M, ff] scratch and dense gu");
-    if (gemm_launch(dY, ldy, WdT, ldw, dact_scratch, ff, M, ff, K, nullptr, nullptr, 0, 0, 0, 0, 1.f, A2, lda2, B2, ldb2, K2, stream)) return -1;
-    return lhrs_swiglu_bwd(dact_scratch, gu, dgu, M, ff, stream);
-  }
-  GemmArgs g; memset(&g, 0, sizeof(g));
-  g.A = (const bf16_t*)dY; g.B = (const bf16_t*)WdT; g.C = dgu; g.M = M; g.N = ff; g.K = K; g.lda = ldy; g.ldb = ldw; g.ldc = ld_gu;
-  g.alpha = 1.f; g.A2 = (const bf16_t*)A2; g.B2 = (const bf16_t*)B2; g.lda2 = lda2; g.ldb2 = ldb2; g.K2 = K2;
-  g.epi = 2; g.ff = ff; g.aux = (const bf16_t*)gu; g.ld_aux = ld_gu;
-  const bool bm144 = pick_144(M, cdiv(ff, 256), K, K2, false);
-  g.tilesM = cdiv(M, bm144 ? 144 : 256); g.tilesN = cdiv(ff, 256);
-  hipStream_t s = (hipStream_t)stream;
-  const int pslot = prof_count(M, ff, K + K2, 2, s);
-  if (bm144) LAUNCH_144(0, 2, grid_256s((long)g.tilesM * g.tilesN), s, g);
-  else LAUNCH_256(0, 2, grid_256s((long)g.tilesM * g.tilesN), s, g);
-  prof_end(pslot, s);
-  LHRS_CHECK_LAUNCH("gemm_swiglu_bwd");
-  return 0;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Small-tile sibling of gemm_fp8_256_kernel (64x128 tile, 4 waves, the 2-stage DMA skeleton of gemm_nt_kernel; a stage row is 128 e4m3
 // bytes = one v_mfma_scale_f32_16x16x128_f8f6f4 step per fragment pair).  Takes the tail rows that the 256x256 kernel would run as a
-// nearly empty last round (see the tail-row rule in gemm_launch).  Same arithmetic and roundings as the big kernel: scale the e4m3 sum by
+// nearly empty last round (the tail-row rule: tail_main_rows, gemm_plan.h).  Same arithmetic and roundings as the big kernel: scale the e4m3 sum by
 // sa[m] * sb[n], add the optional bf16 pair (LoRA) on the same accumulators, * alpha, round to bf16, then add the bf16 residual.
 // ------------------------------------------------------------------------------------------------
 template <int WM_FR, int WN_FR>
@@ -1604,145 +1078,373 @@ __global__ __launch_bounds__(256) void gemm_fp8_small_kernel(GemmArgs g) {
   }
 }
 
+// ==== Host dispatch: an entry point validates its arguments, fills a GemmProblem, and gemm_plan() (gemm_plan.h: every shape rule, no device)
+// lists the launches - rows, kernel, profile kind - that gemm_run() below executes in order =====================================================
+using namespace gemm_plan_h;
+
+// ---- knobs, device facts, workspace -------------------------------------------------------------------------------------------------------
+// the one instance the lhrs_gemm_set_* entry points write; LHRS_GEMM_U4=0: the 16-wave kernels everywhere (kernel A/B tests)
+static GemmKnobs g_knobs = [] { GemmKnobs k; const char* e = getenv("LHRS_GEMM_U4"); k.u4_on = (e == nullptr || e[0] != '0') ? 1 : 0; return k; }();
+// Caller-owned device memory, registered per device (lhrs_gemm_set_workspace; 64 MiB + 4 KiB for 256 CUs).  One user: the tail rows of a
+// row-split product with a long k-loop (GK_SPLITK_TAIL).  Launches that use it must be ordered on ONE stream per device.
+static struct { float* slabs; long units; } g_sk[16];
+
+static int num_cus() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    n = hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0 ? 256 : prop.multiProcessorCount;
+  }
+  return n;
+}
+// a copy of g_knobs with the facts of the calling thread's device filled in (*dev_out: that device, -1 = none)
+static GemmKnobs knobs(int* dev_out = nullptr) {
+  GemmKnobs k = g_knobs;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
+  k.cus = num_cus();
+  k.ws_units = dev >= 0 && g_sk[dev].slabs != nullptr ? g_sk[dev].units : 0;
+  if (dev_out) *dev_out = dev;
+  return k;
+}
+extern "C" int lhrs_gemm_set_u4(int on) { g_knobs.u4_on = on ? 1 : 0; return 0; }
+extern "C" int lhrs_gemm_set_policy(int allow_256) { g_knobs.allow_256 = allow_256 ? 2 : 0; return 0; }
+extern "C" int lhrs_gemm_set_bm144(int mode) { g_knobs.bm144 = mode; return 0; }
+extern "C" int lhrs_gemm_set_min_tiles(int n) { g_knobs.min256 = n; return 0; }
+extern "C" int lhrs_gemm_set_small_thresh(int n) { g_knobs.small_thresh = n; return 0; }
+extern "C" int lhrs_gemm_set_tail_split(int on) { g_knobs.tail_split = on; return 0; }
+extern "C" int lhrs_gemm_set_persistent(int on) { g_knobs.persist = on; return 0; }
+extern "C" long lhrs_gemm_workspace_bytes() { return 4096 + (long)num_cus() * 256 * 256 * 4; }
+// ws == nullptr: forget the workspace of the current device
+extern "C" int lhrs_gemm_set_workspace(void* ws, long bytes) {
+  int dev = 0;
+  LHRS_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16, "gemm_set_workspace: device %d", dev);
+  if (ws == nullptr) { g_sk[dev].slabs = nullptr; g_sk[dev].units = 0; return 0; }
+  LHRS_REQUIRE(bytes >= lhrs_gemm_workspace_bytes() && ((size_t)ws & 255) == 0, "gemm_set_workspace: %ld bytes (need %ld, 256-B aligned)", bytes,
+               lhrs_gemm_workspace_bytes());
+  g_sk[dev].slabs = (float*)((char*)ws + 4096); g_sk[dev].units = num_cus();
+  return 0;
+}
+// ---- the exported rules: pure functions of their arguments and of the knobs ----------------------------------------------------------------
+extern "C" int lhrs_gemm_u4_takes(int M, int N, int K, int lda, int ldb, int ldc, int ldr, int has_bias, int act, int out_f32, int accumulate, float alpha) {
+  return u4_takes(knobs(), M, N, K, lda, ldb, ldc, ldr, has_bias, act, out_f32, accumulate, alpha);
+}
+extern "C" int lhrs_gemm_u4_fused_takes(int kind, int M, int tiles_n, int K, int K2) { return u4_fused_takes(knobs(), kind, M, tiles_n, K, K2); }
+extern "C" int lhrs_gemm_u4_main_rows(int M, int N) { return u4_main_rows(knobs(), M, cdiv(N, 256)); }
+// 1 when lhrs_gemm_swiglu_fwd / _bwd will take the fused kernel for this problem (dense operands), else 0 (they fall back)
+extern "C" int lhrs_gemm_swiglu_fusable(int M, int ff, int K_fwd, int K_bwd, int K2) {
+  const GemmKnobs k = knobs();
+  return swiglu_fusable(k, (long)cdiv(M, 256) * (ff / 128), ff, K_fwd, K2, 8, 8) && swiglu_fusable(k, (long)cdiv(M, 256) * cdiv(ff, 256), ff, K_bwd, K2, 8, 8);
+}
+extern "C" int lhrs_gemm_splitk_splits(int M, int N, int K) { return splitk_f32_splits(M, N, K); }
+extern "C" const char* lhrs_gemm_kernel_name(int kernel) { return kernel >= 0 && kernel < GK_COUNT ? gemm_kernel_info(kernel).name : nullptr; }
+
+static GemmProblem problem(GemmEntry entry, const void* A, long lda, const void* B, long ldb, void* C, int ldc, int M, int N, int K, const void* A2 = nullptr,
+                           int lda2 = 0, const void* B2 = nullptr, int ldb2 = 0, int K2 = 0) {
+  GemmProblem p;
+  p.entry = entry; p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
+  p.A2 = A2; p.lda2 = lda2; p.B2 = B2; p.ldb2 = ldb2; p.K2 = K2;
+  return p;
+}
+// the plan of one call without running it (include/lhrs_hip.h); with cus > 0 no device is asked anything
+extern "C" int lhrs_gemm_plan(int entry, int M, int N, int K, int K2, int flags, int act, float alpha, int lda, int ldb, int ldc, int ldr, int ff, int ld_gu,
+                              int ld_act, int rope_cols, int head_dim, int ptr_align, int cus, int has_workspace, int* out, int cap) {
+  LHRS_REQUIRE(entry >= GE_PLAIN && entry <= GE_SPLITK_F32 && M > 0 && K > 0 && (N > 0 || ff > 0) && out != nullptr, "gemm_plan: entry=%d M=%d N=%d K=%d", entry, M, N, K);
+  GemmKnobs k = cus > 0 ? g_knobs : knobs();
+  if (cus > 0) k.cus = cus;
+  k.ws_units = has_workspace ? k.cus : 0;
+  void* const ptr = (void*)(size_t)(0x10000 + ptr_align);   // never dereferenced: the rules read its alignment only
+  const bool swiglu = entry == GE_SWIGLU_FWD || entry == GE_SWIGLU_BWD;
+  GemmProblem p = problem((GemmEntry)entry, ptr, lda, ptr, ldb, ptr, swiglu ? ld_gu : ldc, M, entry == GE_SWIGLU_FWD ? 2 * ff : swiglu ? ff : N, K,
+                          K2 > 0 ? ptr : nullptr, K2, K2 > 0 ? ptr : nullptr, K2, K2);
+  p.act = act; p.alpha = alpha; p.ldr = ldr; p.bias = flags & 1 ? ptr : nullptr; p.residual = flags & 2 ? ptr : nullptr;
+  p.out_f32 = (flags & 4) != 0 || entry == GE_SPLITK_F32; p.accumulate = (flags & 8) != 0; p.drop_thresh = flags & 16 ? 1 : 0;
+  p.ff = ff; p.gu = p.act_out = p.scratch = ptr; p.ld_gu = ld_gu; p.ld_act = ld_act;
+  p.rope_cos = p.rope_sin = (const float*)ptr; p.rope_mod = 4096; p.rope_cols = rope_cols; p.head_dim = head_dim;
+  GemmSeg segs[GEMM_PLAN_CAP];
+  const int n = gemm_plan(p, k, segs, GEMM_PLAN_CAP);
+  LHRS_REQUIRE(n > 0 && n <= cap, "gemm_plan: %d segments, room for %d", n, cap);
+  for (int i = 0; i < n; ++i) { out[4 * i] = segs[i].row0; out[4 * i + 1] = segs[i].row1; out[4 * i + 2] = segs[i].kernel; out[4 * i + 3] = segs[i].prof_kind; }
+  return n;
+}
+// ---- the executor -------------------------------------------------------------------------------------------------------------------------
+// the persistent kernels: at most one workgroup per CU, workgroup b takes tiles b, b + grid, ...; lhrs_gemm_set_persistent(0): one per tile
+static dim3 grid_256s(const GemmArgs& g) {
+  const long tiles = (long)g.tilesM * g.tilesN;
+  return dim3((unsigned)(g_knobs.persist ? (tiles < num_cus() ? tiles : num_cus()) : tiles));
+}
+// a second operand pair (K2 > 0: the fused LoRA product) is a template parameter of the 256-row kernel
+template <int ACT, int EPI>
+static void launch_256s(GemmArgs& g, hipStream_t s) {
+  if (g.K2 > 0) hipLaunchKernelGGL((gemm_nt_256s_kernel<ACT, EPI, true>), grid_256s(g), dim3(1024), 0, s, g);
+  else hipLaunchKernelGGL((gemm_nt_256s_kernel<ACT, EPI, false>), grid_256s(g), dim3(1024), 0, s, g);
+}
+template <int ACT, int EPI>
+static void launch_144s(GemmArgs& g, hipStream_t s) { hipLaunchKernelGGL((gemm_nt_144s_kernel<ACT, EPI>), grid_256s(g), dim3(768), 0, s, g); }
+template <int WM, int WN, int ACT>
+static void launch_tile(GemmArgs& g, hipStream_t s) { hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, ACT>), dim3(g.tilesM * g.tilesN), dim3(256), 0, s, g); }
+// f(std::integral_constant<int, act>): the activation is a template parameter of the plain-epilogue kernels
+template <class F>
+static void by_act(int act, F f) {
+  switch (act) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 3>{}); break;
+  }
+}
+static int check_plain(const GemmProblem& q) {
+  LHRS_REQUIRE(q.K % 64 == 0, "gemm: K=%d must be a multiple of 64 (zero-pad the reduction dim)", q.K);
+  LHRS_REQUIRE(q.N % 4 == 0, "gemm: N=%d must be a multiple of 4", q.N);
+  LHRS_REQUIRE(q.lda % 8 == 0 && q.ldb % 8 == 0, "gemm: lda=%d ldb=%d must be multiples of 8 (16-B rows)", (int)q.lda, (int)q.ldb);
+  LHRS_REQUIRE(q.ldc % 4 == 0 && (q.residual == nullptr || q.ldr % 4 == 0), "gemm: ldc/ldr must be multiples of 4");
+  LHRS_REQUIRE(q.lda >= q.K && q.ldb >= q.K && q.ldc >= q.N, "gemm: leading dims too small");
+  LHRS_REQUIRE(!q.accumulate || q.out_f32, "gemm: accumulate needs f32 output");
+  LHRS_REQUIRE(q.act >= 0 && q.act <= 3, "gemm: unknown activation %d", q.act);
+  return 0;
+}
+// the kernel arguments of one segment: the problem's, with every row-indexed operand moved to row0 and the tile counts of the segment's kernel
+static GemmArgs seg_args(const GemmProblem& q, const GemmSeg& sg) {
+  GemmArgs g; memset(&g, 0, sizeof(g));
+  const long r = sg.row0, esz = q.out_f32 ? 4 : 2, asz = q.entry == GE_FP8 || q.entry == GE_INT8 ? 1 : 2;
+  auto at_row = [r](const void* ptr, long ld, long size) { return ptr ? (char*)ptr + r * ld * size : nullptr; };
+  g.A = (const bf16_t*)at_row(q.A, q.lda, asz); g.B = (const bf16_t*)q.B; g.C = at_row(q.C, q.ldc, esz);
+  g.bias = (const bf16_t*)q.bias; g.res = (const bf16_t*)at_row(q.residual, q.ldr, 2);
+  g.M = sg.row1 - sg.row0; g.N = q.N; g.K = q.K; g.lda = (int)q.lda; g.ldb = (int)q.ldb; g.ldc = q.ldc; g.ldr = q.ldr;
+  g.alpha = q.alpha; g.act = q.act; g.out_f32 = q.out_f32; g.accum = q.accumulate;
+  g.A2 = (const bf16_t*)at_row(q.A2, q.lda2, 2); g.B2 = (const bf16_t*)q.B2; g.lda2 = q.lda2; g.ldb2 = q.ldb2; g.K2 = q.K2;
+  g.sa = q.sa ? q.sa + r : nullptr; g.sb = q.sb; g.k2_dev = q.k2_dev;
+  g.drop_scale = q.drop_scale; g.drop_seed = q.drop_seed; g.drop_thresh = q.drop_thresh;
+  const GemmKernelInfo& ki = gemm_kernel_info(sg.kernel);
+  g.tilesM = cdiv(g.M, ki.bm); g.tilesN = cdiv(g.N, ki.bn);
+  switch (q.entry) {   // the fused epilogues of the 16-wave kernels
+    case GE_SWIGLU_FWD: g.epi = 1; g.ff = q.ff; g.aux_out = (bf16_t*)at_row(q.act_out, q.ld_act, 2); g.ld_aux = q.ld_act; break;
+    case GE_SWIGLU_BWD: g.epi = 2; g.ff = q.ff; g.aux = (const bf16_t*)at_row(q.gu, q.ld_gu, 2); g.ld_aux = q.ld_gu; break;
+    case GE_ROPE: g.epi = 3; g.rope_cos = q.rope_cos; g.rope_sin = q.rope_sin; g.rope_mod = q.rope_mod; g.rope_pos0 = q.rope_pos0; g.rope_cols = q.rope_cols; break;
+    default: break;
+  }
+  return g;
+}
+// split-K of the 128x128 kernel: `splits` k-slabs across blockIdx.y, each an f32 [rows, N] image in `slabs`, summed in a fixed order by one small
+// launch - into bf16 C with alpha and the residual (the tail rows), or into f32 C (lhrs_gemm_bf16_nt_splitk_f32)
+static void launch_splitk(const GemmProblem& q, const GemmSeg& sg, GemmArgs g, float* slabs, hipStream_t s) {
+  void* const C = g.C; const bf16_t* const res = g.res;
+  const int ks = cdiv(q.K / 64, sg.splits) * 64, used = cdiv(q.K, ks);
+  g.C = slabs; g.ldc = q.N; g.res = nullptr; g.ldr = 0; g.alpha = 1.f; g.out_f32 = 1; g.accum = 0; g.ksplit = ks;
+  const dim3 grid(g.tilesM * g.tilesN, used);
+  if (sg.kernel == GK_T64X128) hipLaunchKernelGGL((gemm_nt_kernel<2, 4, 0>), grid, dim3(256), 0, s, g);       // the skinny-N product
+  else if (sg.kernel == GK_T64X64) hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 0>), grid, dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((gemm_nt_kernel<4, 4, 0>), grid, dim3(256), 0, s, g);
+  const long work = (long)g.M * (q.N / 4);
+  int rg = (int)((work + 255) / 256); if (rg > 8192) rg = 8192;
+  if (!q.out_f32) hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rg), dim3(256), 0, s, (const float*)slabs, (bf16_t*)C, (long)q.ldc, g.M, q.N, used, q.alpha, res, (long)q.ldr);
+  else hipLaunchKernelGGL(splitk_reduce_f32_kernel, dim3(rg), dim3(256), 0, s, (const float*)slabs, (float*)C, (long)q.ldc, g.M, q.N, used);
+}
+// The four-wave kernels keep their own argument block (gemm_u4.hip); their wrappers cannot decline: the planner asked their predicates.
+static int seg_launch(const GemmProblem& q, const GemmSeg& sg, int dev, hipStream_t s) {
+  GemmArgs g = seg_args(q, sg);
+  const dim3 tiles(g.tilesM * g.tilesN);
+  int u4 = 0;
+  switch (sg.kernel) {
+    case GK_256: by_act(g.act, [&](auto a) { launch_256s<decltype(a)::value, 0>(g, s); }); break;
+    case GK_144: by_act(g.act, [&](auto a) { launch_144s<decltype(a)::value, 0>(g, s); }); break;
+    case GK_T128: by_act(g.act, [&](auto a) { launch_tile<4, 4, decltype(a)::value>(g, s); }); break;
+    case GK_T64X128: by_act(g.act, [&](auto a) { launch_tile<2, 4, decltype(a)::value>(g, s); }); break;
+    case GK_T64X64: by_act(g.act, [&](auto a) { launch_tile<2, 2, decltype(a)::value>(g, s); }); break;
+    case GK_SWIGLU_FWD_256: launch_256s<0, 1>(g, s); break;
+    case GK_SWIGLU_FWD_144: launch_144s<0, 1>(g, s); break;
+    case GK_SWIGLU_BWD_256: launch_256s<0, 2>(g, s); break;
+    case GK_SWIGLU_BWD_144: launch_144s<0, 2>(g, s); break;
+    case GK_ROPE_256: launch_256s<0, 3>(g, s); break;
+    case GK_ROPE_144: launch_144s<0, 3>(g, s); break;
+    case GK_FP8_256: hipLaunchKernelGGL(gemm_fp8_256_kernel<false>, tiles, dim3(512), 0, s, g); break;
+    case GK_I8_256: hipLaunchKernelGGL(gemm_fp8_256_kernel<true>, tiles, dim3(512), 0, s, g); break;
+    case GK_FP8_SMALL: hipLaunchKernelGGL((gemm_fp8_small_kernel<2, 4>), tiles, dim3(256), 0, s, g); break;
+    case GK_SPLITK_TAIL:
+      LHRS_REQUIRE(dev >= 0 && g_sk[dev].slabs != nullptr, "gemm: the split-K tail rows need the registered workspace");
+      launch_splitk(q, sg, g, g_sk[dev].slabs, s);
+      break;
+    case GK_SPLITK_F32: launch_splitk(q, sg, g, (float*)q.scratch, s); break;
+    case GK_U4:
+      u4 = lhrs_gemm_u4_nt_lora(g.A, g.lda, g.B, g.ldb, g.A2, g.lda2, g.B2, g.ldb2, g.K2, g.C, g.ldc, g.M, g.N, g.K, g.res, g.ldr, s);   // K2 = 0: no pair
+      break;
+    case GK_U4_SWIGLU_FWD: u4 = lhrs_gemm_u4_swiglu_fwd(g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.aux_out, (int)g.ld_aux, g.M, g.ff, g.K, s); break;
+    case GK_U4_SWIGLU_BWD: u4 = lhrs_gemm_u4_swiglu_bwd(g.A, g.lda, g.B, g.ldb, g.aux, g.C, g.ldc, g.M, g.ff, g.K, s); break;
+    case GK_U4_ROPE:
+      u4 = lhrs_gemm_u4_rope_lora(g.A, g.lda, g.B, g.ldb, g.A2, g.lda2, g.B2, g.ldb2, g.K2, g.C, g.ldc, g.M, g.N, g.K, g.rope_cos, g.rope_sin, g.rope_mod,
+                                  g.rope_pos0, g.rope_cols, s);
+      break;
+    default: LHRS_FAIL("gemm: no launch for kernel %d", sg.kernel);
+  }
+  LHRS_REQUIRE(u4 <= 0, "gemm: the four-wave kernel declined a planned launch (%s)", gemm_kernel_info(sg.kernel).name);
+  return u4;
+}
+// The elementwise pass of an unfused fallback (elementwise.hip) on what the segments wrote.  Only SwiGLU forward is ever planned in row
+// ranges; the passes of SwiGLU backward and RoPE always cover the whole result (the plain product in front of them may be row-split).
+static int seg_pass(const GemmProblem& p, const GemmSeg& sg, hipStream_t s) {
+  const long r0 = sg.pass_row0, rows = sg.row1 - r0;
+  switch (p.entry) {
+    case GE_SWIGLU_FWD:
+      LHRS_REQUIRE(p.ld_gu == 2 * p.ff && p.ld_act == p.ff, "gemm_swiglu_fwd: the unfused fallback needs dense gu / act");
+      return lhrs_swiglu_fwd((bf16_t*)p.C + r0 * p.ld_gu, (bf16_t*)p.act_out + r0 * p.ld_act, rows, p.ff, s);
+    case GE_SWIGLU_BWD: return lhrs_swiglu_bwd(p.scratch, p.gu, p.C, p.M, p.ff, s);
+    case GE_ROPE: return lhrs_rope(p.C, p.ldc, p.M, p.rope_cols / p.head_dim, p.head_dim, p.rope_cos, p.rope_sin, nullptr, p.rope_mod, p.rope_pos0, 0, s);
+    default: LHRS_FAIL("gemm: no elementwise pass for entry %d", (int)p.entry);
+  }
+}
+// Runs a plan.  Every segment is counted in the live profile; one with a prof_kind is bracketed by HIP events when its kind's sampling
+// stride takes it (the fused-epilogue kinds count towards the GEMM FLOPs but are not "the dominant kernel" of lhrs_gemm_profile_read).
+static int gemm_run(const GemmProblem& p, void* stream, const char* what) {
+  LHRS_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
+  int dev = -1;
+  const GemmKnobs k = knobs(&dev);
+  GemmSeg segs[GEMM_PLAN_CAP];
+  const int n = gemm_plan(p, k, segs, GEMM_PLAN_CAP);
+  LHRS_REQUIRE(n > 0, "gemm: the plan outgrew GEMM_PLAN_CAP");
+  hipStream_t s = (hipStream_t)stream;
+  LHRS_REQUIRE(p.entry != GE_SWIGLU_BWD || segs[n - 1].pass_row0 < 0 || (p.scratch != nullptr && p.ld_gu == 2 * p.ff),
+               "gemm_swiglu_bwd: the unfused fallback needs a [M, ff] scratch and dense gu");
+  for (int i = 0; i < n; ++i) {
+    const GemmSeg& sg = segs[i];
+    const GemmProblem q = gemm_seg_problem(p, sg.kernel, sg.part);
+    if (gemm_kernel_info(sg.kernel).plain && check_plain(q)) return -1;
+    int slot = -1;
+    if (g_prof.on) {
+      // (the four-wave RoPE launch has always been counted without its LoRA pair)
+      const double flops = 2.0 * (sg.row1 - sg.row0) * q.N * (q.K + (sg.kernel == GK_U4_ROPE ? 0 : q.K2));
+      g_prof.launches_all++; g_prof.total_flops_all += flops;
+      if (sg.prof_kind >= 0 && g_prof.used < g_prof.cap && g_prof.take(sg.prof_kind)) {
+        slot = g_prof.used++;
+        g_prof.flops[slot] = flops; g_prof.kind[slot] = sg.prof_kind;
+        (void)hipEventRecord(g_prof.ev[2 * slot], s);
+      }
+    }
+    if (seg_launch(q, sg, dev, s)) return -1;
+    if (slot >= 0) (void)hipEventRecord(g_prof.ev[2 * slot + 1], s);
+    LHRS_CHECK_LAUNCH(what);
+    if (sg.pass_row0 >= 0 && seg_pass(p, sg, s)) return -1;
+  }
+  return 0;
+}
+// ---- C ABI ----------------------------------------------------------------------------------------------------------------------------------
+extern "C" int lhrs_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const void* bias, const void* residual,
+                                 int ldr, int act, int out_f32, int accumulate, float alpha, void* stream) {
+  GemmProblem p = problem(GE_PLAIN, A, lda, B, ldb, C, ldc, M, N, K);
+  p.bias = bias; p.residual = residual; p.ldr = ldr; p.act = act; p.out_f32 = out_f32; p.accumulate = accumulate; p.alpha = alpha;
+  return gemm_run(p, stream, "gemm_bf16_nt");
+}
+
+// ... + A2.B2^T: the rank-K2 LoRA update rides in the k-loop of the base GEMM (K2 / 64 more stages of either kernel family; bit-identical)
+extern "C" int lhrs_gemm_bf16_nt_lora(const void* A, int lda, const void* B, int ldb, const void* A2, int lda2, const void* B2, int ldb2, int K2, void* C, int ldc,
+                                      int M, int N, int K, const void* bias, const void* residual, int ldr, int out_f32, int accumulate, float alpha, void* stream) {
+  LHRS_REQUIRE(A2 && B2 && K2 > 0 && K2 % 64 == 0 && lda2 % 8 == 0 && ldb2 % 8 == 0 && lda2 >= K2 && ldb2 >= K2,
+               "gemm_lora: bad second operand pair (K2=%d lda2=%d ldb2=%d)", K2, lda2, ldb2);
+  GemmProblem p = problem(GE_PLAIN, A, lda, B, ldb, C, ldc, M, N, K, A2, lda2, B2, ldb2, K2);
+  p.bias = bias; p.residual = residual; p.ldr = ldr; p.out_f32 = out_f32; p.accumulate = accumulate; p.alpha = alpha;
+  return gemm_run(p, stream, "gemm_bf16_nt");
+}
+
+// C = mask * (alpha * A.B^T) / (1 - p) + residual, mask = the counter-based LoRA dropout mask over the [M, N] result (see common.h)
+extern "C" int lhrs_gemm_bf16_nt_dropmask(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const void* residual, int ldr,
+                                          float alpha, float p_drop, unsigned seed, void* stream) {
+  LHRS_REQUIRE(p_drop > 0.f && p_drop < 1.f, "gemm_dropmask: p=%f", p_drop);
+  GemmProblem p = problem(GE_PLAIN, A, lda, B, ldb, C, ldc, M, N, K);
+  p.residual = residual; p.ldr = ldr; p.alpha = alpha;
+  p.drop_scale = 1.f / (1.f - p_drop); p.drop_seed = seed; p.drop_thresh = (unsigned)((double)p_drop * 4294967296.0);
+  return gemm_run(p, stream, "gemm_bf16_nt");
+}
+
+// LLaMA MLP with the SwiGLU / SwiGLU' fused into the GEMM epilogue (include/lhrs_hip.h): one launch, bit-identical to GEMM + lhrs_swiglu_fwd /
+// _bwd, which is also the fallback for shapes the fused kernels do not take (swiglu_fusable)
+extern "C" int lhrs_gemm_swiglu_fwd(const void* X, int ldx, const void* Wgu, int ldw, const void* A2, int lda2, const void* B2, int ldb2, int K2, void* gu, int ld_gu,
+                                    void* act, int ld_act, int M, int ff, int K, void* stream) {
+  LHRS_REQUIRE(M > 0 && ff > 0 && K > 0 && ff % 8 == 0 && ld_gu >= 2 * ff && ld_act >= ff && ld_gu % 8 == 0 && ld_act % 8 == 0,
+               "gemm_swiglu_fwd: M=%d ff=%d K=%d ld_gu=%d ld_act=%d", M, ff, K, ld_gu, ld_act);
+  GemmProblem p = problem(GE_SWIGLU_FWD, X, ldx, Wgu, ldw, gu, ld_gu, M, 2 * ff, K, A2, lda2, B2, ldb2, K2);
+  p.ff = ff; p.ld_gu = ld_gu; p.act_out = act; p.ld_act = ld_act;
+  return gemm_run(p, stream, "gemm_swiglu_fwd");
+}
+
+extern "C" int lhrs_gemm_swiglu_bwd(const void* dY, int ldy, const void* WdT, int ldw, const void* A2, int lda2, const void* B2, int ldb2, int K2, const void* gu,
+                                    void* dgu, int ld_gu, void* dact_scratch, int M, int ff, int K, void* stream) {
+  LHRS_REQUIRE(M > 0 && ff > 0 && K > 0 && ff % 8 == 0 && ld_gu >= 2 * ff && ld_gu % 8 == 0, "gemm_swiglu_bwd: M=%d ff=%d K=%d ld_gu=%d", M, ff, K, ld_gu);
+  GemmProblem p = problem(GE_SWIGLU_BWD, dY, ldy, WdT, ldw, dgu, ld_gu, M, ff, K, A2, lda2, B2, ldb2, K2);
+  p.ff = ff; p.gu = gu; p.ld_gu = ld_gu; p.scratch = dact_scratch;
+  return gemm_run(p, stream, "gemm_swiglu_bwd");
+}
+
+// qkv projection with the RoPE of its q / k heads in the GEMM epilogue; bit-identical to lhrs_gemm_bf16_nt(_lora) + lhrs_rope, which is also
+// the fallback when the fused kernels do not apply (rope_fusable)
+extern "C" int lhrs_gemm_rope_fwd(const void* X, int ldx, const void* W, int ldw, const void* A2, int lda2, const void* B2, int ldb2, int K2, void* C, int ldc, int M,
+                                  int N, int K, const float* cos_t, const float* sin_t, int pos_mod, int pos0, int rope_cols, int head_dim, void* stream) {
+  LHRS_REQUIRE(M > 0 && N > 0 && K > 0 && head_dim % 16 == 0 && rope_cols >= 0 && rope_cols <= N && rope_cols % head_dim == 0 && pos_mod > 0 &&
+                   cos_t && sin_t && ldc % 8 == 0,
+               "gemm_rope_fwd: M=%d N=%d K=%d rope_cols=%d head_dim=%d pos_mod=%d", M, N, K, rope_cols, head_dim, pos_mod);
+  GemmProblem p = problem(GE_ROPE, X, ldx, W, ldw, C, ldc, M, N, K, A2, lda2, B2, ldb2, K2);
+  p.rope_cos = cos_t; p.rope_sin = sin_t; p.rope_mod = pos_mod; p.rope_pos0 = pos0; p.rope_cols = rope_cols; p.head_dim = head_dim;
+  return gemm_run(p, stream, "gemm_rope_fwd");
+}
+
 // C[M, N] (bf16) = alpha * sa[m] * sb[n] * (A8[M, K] . B8[N, K]^T) (+ residual): e4m3 operands with per-row fp32 scales
-// (lhrs_quant_fp8_rows).  K % 128 == 0, N % 8 == 0; lda / ldb in BYTES (>= K, multiples of 16).
-static int gemm_fp8_launch(const void* A8, long lda, const float* sa, const void* B8, long ldb, const float* sb, const void* A2, int lda2,
-                           const void* B2, int ldb2, int K2, void* C, int ldc, int M, int N, int K, const void* residual, int ldr,
-                           float alpha, void* stream, bool i8 = false, const int* k2_dev = nullptr) {
+// (lhrs_quant_fp8_rows).  K % 128 == 0, N % 8 == 0; lda / ldb in BYTES (>= K, multiples of 16).  The tile rows that spill over the last full
+// round of the CUs go to the small-tile sibling (the tail-row rule); int8 has no such sibling and takes no split.
+static int gemm_8bit(GemmEntry entry, const void* A8, long lda, const float* sa, const void* B8, long ldb, const float* sb, const void* A2, int lda2, const void* B2,
+                     int ldb2, int K2, const int* k2_dev, void* C, int ldc, int M, int N, int K, const void* residual, int ldr, float alpha, void* stream) {
   LHRS_REQUIRE(M > 0 && N > 0 && K >= 256 && K % 128 == 0, "gemm_fp8: M=%d N=%d K=%d (K %% 128 == 0, K >= 256)", M, N, K);
   LHRS_REQUIRE(lda % 16 == 0 && ldb % 16 == 0 && lda >= K && ldb >= K && sa && sb, "gemm_fp8: lda=%ld ldb=%ld", lda, ldb);
   LHRS_REQUIRE(N % 8 == 0 && ldc % 8 == 0 && ldc >= N && (residual == nullptr || ldr % 8 == 0), "gemm_fp8: N=%d ldc=%d ldr=%d", N, ldc, ldr);
   LHRS_REQUIRE((K2 == 0 && !k2_dev) || (A2 && B2 && K2 % 64 == 0 && lda2 % 8 == 0 && ldb2 % 8 == 0 && lda2 >= K2 && ldb2 >= K2),
                "gemm_fp8: bad bf16 pair (K2=%d lda2=%d ldb2=%d)", K2, lda2, ldb2);
-  // tail-row rule (see gemm_launch): the tile rows that spill over the last full round of the 256 CUs go to the small-tile kernel
-  if (!i8 && t_split_ok && g_gemm_tail_split) {   // (the small-tile sibling exists for e4m3 only)
-    const int tm = cdiv(M, 256), tn = cdiv(N, 256);
-    const long T = (long)tm * tn, rounds = (T + 255) / 256, full = T / 256;
-    const int tm_main = (int)(full * 256 / tn);
-    if (full >= 1 && T % 256 != 0 && tm_main >= 1 && tm_main < tm) {
-      const long t_main = (long)tm_main * tn, t_tail = T - t_main;
-      if ((double)((t_main + 255) / 256) + 2.5 * (double)t_tail / 256.0 + 0.05 < (double)rounds) {
-        const int M_main = tm_main * 256;
-        t_split_ok = false;
-        int rc = gemm_fp8_launch(A8, lda, sa, B8, ldb, sb, A2, lda2, B2, ldb2, K2, C, ldc, M_main, N, K, residual, ldr, alpha, stream);
-        t_split_ok = true;
-        if (rc) return rc;
-        GemmArgs h; memset(&h, 0, sizeof(h));
-        h.A = (const bf16_t*)((const char*)A8 + (long)M_main * lda); h.B = (const bf16_t*)B8; h.C = (bf16_t*)C + (long)M_main * ldc;
-        h.res = residual ? (const bf16_t*)residual + (long)M_main * ldr : nullptr;
-        h.M = M - M_main; h.N = N; h.K = K; h.lda = (int)lda; h.ldb = (int)ldb; h.ldc = ldc; h.ldr = ldr; h.alpha = alpha; h.sa = sa + M_main; h.sb = sb;
-        h.A2 = A2 ? (const bf16_t*)A2 + (long)M_main * lda2 : nullptr; h.B2 = (const bf16_t*)B2; h.lda2 = lda2; h.ldb2 = ldb2; h.K2 = K2;
-        h.tilesM = cdiv(h.M, 64); h.tilesN = cdiv(N, 128);
-        if (g_prof.on) { g_prof.launches_all++; g_prof.total_flops_all += 2.0 * h.M * N * (K + K2); }
-        hipLaunchKernelGGL((gemm_fp8_small_kernel<2, 4>), dim3(h.tilesM * h.tilesN), dim3(256), 0, (hipStream_t)stream, h);
-        LHRS_CHECK_LAUNCH("gemm_fp8_nt (tail rows)");
-        return 0;
-      }
-    }
-  }
-  GemmArgs g; memset(&g, 0, sizeof(g));
-  g.A = (const bf16_t*)A8; g.B = (const bf16_t*)B8; g.C = C; g.res = (const bf16_t*)residual;
-  g.M = M; g.N = N; g.K = K; g.lda = (int)lda; g.ldb = (int)ldb; g.ldc = ldc; g.ldr = ldr; g.alpha = alpha; g.sa = sa; g.sb = sb;
-  g.A2 = (const bf16_t*)A2; g.B2 = (const bf16_t*)B2; g.lda2 = lda2; g.ldb2 = ldb2; g.K2 = K2; g.k2_dev = k2_dev;
-  g.tilesM = cdiv(M, 256); g.tilesN = cdiv(N, 256);
-  if (g_prof.on) { g_prof.launches_all++; g_prof.total_flops_all += 2.0 * M * N * (K + K2); }
-  if (i8) hipLaunchKernelGGL(gemm_fp8_256_kernel<true>, dim3(g.tilesM * g.tilesN), dim3(512), 0, (hipStream_t)stream, g);
-  else hipLaunchKernelGGL(gemm_fp8_256_kernel<false>, dim3(g.tilesM * g.tilesN), dim3(512), 0, (hipStream_t)stream, g);
-  LHRS_CHECK_LAUNCH("gemm_fp8_nt");
-  return 0;
+  GemmProblem p = problem(entry, A8, lda, B8, ldb, C, ldc, M, N, K, A2, lda2, B2, ldb2, K2);
+  p.k2_dev = k2_dev;   // (int8: the pair may have device-known columns only)
+  p.residual = residual; p.ldr = ldr; p.alpha = alpha; p.sa = sa; p.sb = sb;
+  return gemm_run(p, stream, "gemm_fp8_nt");
 }
-
-// LLM.int8 product (int8.hip): C[M, N] (bf16) = alpha * (sa[m] * sb[n] * (A8 . B8^T in int32) + A2[M, :K2t] . B2[N, :K2t]^T) (+ residual).
-// A8 / B8: int8 rows (lhrs_int8_prepare / lhrs_quant_int8_rows), sa / sb their dequantisation factors absmax / 127.  The bf16 pair holds
-// K2 host-known columns (a LoRA update; 0 = none) followed by k2_dev[0] device-known ones (the 16-bit outlier-column product, a multiple of
-// 64 written by lhrs_int8_prepare into meta[1]); K2t is their sum, lda2 / ldb2 must cover the worst case.  K % 128 == 0, K2 % 64 == 0.
-extern "C" int lhrs_gemm_int8_nt(const void* A8, long lda, const float* sa, const void* B8, long ldb, const float* sb, const void* A2,
-                                 int lda2, const void* B2, int ldb2, int K2, const int* k2_dev, void* C, int ldc, int M, int N, int K,
-                                 const void* residual, int ldr, float alpha, void* stream) {
-  return gemm_fp8_launch(A8, lda, sa, B8, ldb, sb, A2, lda2, B2, ldb2, K2, C, ldc, M, N, K, residual, ldr, alpha, stream, true, k2_dev);
+extern "C" int lhrs_gemm_fp8_nt(const void* A8, long lda, const float* sa, const void* B8, long ldb, const float* sb, void* C, int ldc, int M, int N, int K,
+                                const void* residual, int ldr, float alpha, void* stream) {
+  return gemm_8bit(GE_FP8, A8, lda, sa, B8, ldb, sb, nullptr, 0, nullptr, 0, 0, nullptr, C, ldc, M, N, K, residual, ldr, alpha, stream);
 }
-
-
-extern "C" int lhrs_gemm_fp8_nt(const void* A8, long lda, const float* sa, const void* B8, long ldb, const float* sb, void* C, int ldc,
-                                int M, int N, int K, const void* residual, int ldr, float alpha, void* stream) {
-  return gemm_fp8_launch(A8, lda, sa, B8, ldb, sb, nullptr, 0, nullptr, 0, 0, C, ldc, M, N, K, residual, ldr, alpha, stream);
-}
-
 // ... + alpha * A2[M, K2] . B2[N, K2]^T in bf16 on the same accumulators (the LoRA update of an 8-bit base linear), K2 % 64 == 0
-extern "C" int lhrs_gemm_fp8_nt_lora(const void* A8, long lda, const float* sa, const void* B8, long ldb, const float* sb, const void* A2,
-                                     int lda2, const void* B2, int ldb2, int K2, void* C, int ldc, int M, int N, int K,
-                                     const void* residual, int ldr, float alpha, void* stream) {
+extern "C" int lhrs_gemm_fp8_nt_lora(const void* A8, long lda, const float* sa, const void* B8, long ldb, const float* sb, const void* A2, int lda2, const void* B2,
+                                     int ldb2, int K2, void* C, int ldc, int M, int N, int K, const void* residual, int ldr, float alpha, void* stream) {
   LHRS_REQUIRE(K2 > 0, "gemm_fp8_lora: K2=%d", K2);
-  return gemm_fp8_launch(A8, lda, sa, B8, ldb, sb, A2, lda2, B2, ldb2, K2, C, ldc, M, N, K, residual, ldr, alpha, stream);
+  return gemm_8bit(GE_FP8, A8, lda, sa, B8, ldb, sb, A2, lda2, B2, ldb2, K2, nullptr, C, ldc, M, N, K, residual, ldr, alpha, stream);
+}
+// LLM.int8 product: int8 operands, int32 accumulation; the bf16 pair holds K2 host-known columns and k2_dev[0] device-known outlier columns
+extern "C" int lhrs_gemm_int8_nt(const void* A8, long lda, const float* sa, const void* B8, long ldb, const float* sb, const void* A2, int lda2, const void* B2,
+                                 int ldb2, int K2, const int* k2_dev, void* C, int ldc, int M, int N, int K, const void* residual, int ldr, float alpha, void* stream) {
+  return gemm_8bit(GE_INT8, A8, lda, sa, B8, ldb, sb, A2, lda2, B2, ldb2, K2, k2_dev, C, ldc, M, N, K, residual, ldr, alpha, stream);
 }
 
+// long-K, few-tile product with f32 output (the projector's weight gradients): split-K through f32 slabs of `workspace`; 1 split: a plain launch
+extern "C" int lhrs_gemm_bf16_nt_splitk_f32(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K, float* workspace, void* stream) {
+  LHRS_REQUIRE(M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 4 == 0 && ldc % 4 == 0 && ldc >= N && lda % 8 == 0 && ldb % 8 == 0 && lda >= K && ldb >= K,
+               "gemm_splitk_f32: M=%d N=%d K=%d lda=%d ldb=%d ldc=%d", M, N, K, lda, ldb, ldc);
+  const int splits = splitk_f32_splits(M, N, K);
+  LHRS_REQUIRE(splits == 1 || workspace != nullptr, "gemm_splitk_f32: %d splits need a workspace of splits * M * N floats", splits);
+  GemmProblem p = problem(GE_SPLITK_F32, A, lda, B, ldb, C, ldc, M, N, K);
+  p.out_f32 = 1; p.scratch = workspace;
+  return gemm_run(p, stream, "gemm_splitk_f32");
+}
 
-// Skinny-N product C[M, N] (bf16) = alpha * A[M, K] . B[N, K]^T for N <= 384 (the LoRA down-projections x.A^T / dy.B, peft lora.Linear):
-// HBM-bound on A, but one 64-row block walking all of K with a two-stage pipeline is latency-bound (74 us at M = 8190, K = 4096);
-// here K is split `lhrs_gemm_skinny_splits(K, N)` ways across blockIdx.y into f32 slabs of the workspace, then summed (~15 us).
-// workspace: lhrs_gemm_skinny_splits(K, N) * M * N floats.
+// Skinny-N product (N <= 384: the LoRA down-projections): HBM-bound on A, latency-bound as one 64-row block per tile walking all of K, so K is
+// split lhrs_gemm_skinny_splits(K, N) ways into f32 slabs of the workspace, then summed.  No rule beyond its split count: no plan.
 extern "C" int lhrs_gemm_skinny_splits(int K, int N) {
   int s = K / 512;
   const int cap = N <= 128 ? 16 : 4;  // wide adapters: the f32 slabs (splits * M * N * 4 B) soon cost more than the latency they hide
   return s < 1 ? 1 : (s > cap ? cap : s);
 }
-
 extern "C" int lhrs_gemm_bf16_nt_skinny(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, float alpha,
                                         float* workspace, void* stream) {
   LHRS_REQUIRE(M > 0 && N > 0 && N <= 384 && N % 64 == 0 && K % 64 == 0 && workspace != nullptr, "gemm_skinny: M=%d N=%d K=%d", M, N, K);
   LHRS_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && lda >= K && ldb >= K && ldc >= N && ldc % 4 == 0, "gemm_skinny: lda=%d ldb=%d ldc=%d", lda, ldb, ldc);
-  const int splits = lhrs_gemm_skinny_splits(K, N);
-  int ks = cdiv(K / 64, splits) * 64;
-  GemmArgs g; memset(&g, 0, sizeof(g));
-  g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = workspace; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = N;
-  g.alpha = 1.f; g.out_f32 = 1; g.ksplit = ks;
-  const bool wide = N % 128 == 0;  // 64x128 tiles: the rows of A are read once per 128 columns, not per 64 (M = 8190: 5-11 % faster)
-  g.tilesM = cdiv(M, 64); g.tilesN = cdiv(N, wide ? 128 : 64);
-  const int used = cdiv(K, ks);
-  hipStream_t s = (hipStream_t)stream;
+  GemmProblem p = problem(GE_PLAIN, A, lda, B, ldb, C, ldc, M, N, K);
+  p.alpha = alpha;
+  // 64x128 tiles when N allows: the rows of A are read once per 128 columns, not per 64 (M = 8190: 5-11 % faster)
+  const GemmSeg sg{0, M, N % 128 == 0 ? GK_T64X128 : GK_T64X64, -1, lhrs_gemm_skinny_splits(K, N), GP_WHOLE, -1};
   if (g_prof.on) { g_prof.launches_all++; g_prof.total_flops_all += 2.0 * M * N * K; }
-  if (wide) hipLaunchKernelGGL((gemm_nt_kernel<2, 4, 0>), dim3(g.tilesM * g.tilesN, used), dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 0>), dim3(g.tilesM * g.tilesN, used), dim3(256), 0, s, g);
+  launch_splitk(p, sg, seg_args(p, sg), workspace, (hipStream_t)stream);
   LHRS_CHECK_LAUNCH("gemm_skinny");
-  const long work = (long)M * (N / 4);
-  int rg = (int)((work + 255) / 256); if (rg > 8192) rg = 8192;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rg), dim3(256), 0, s, workspace, (bf16_t*)C, (long)ldc, M, N, used, alpha);
-  LHRS_CHECK_LAUNCH("gemm_skinny_reduce");
-  return 0;
-}
-
-
-// Long-K, few-tile product with f32 output (the projector's weight gradients dW = dY^T X over the token dimension: K = B * 912 = 27392
-// against 2048 x 1024 outputs = 128 tiles of 128^2 for 256 CUs): K is split `lhrs_gemm_splitk_splits` ways across blockIdx.y into f32 slabs
-// of the workspace (splits * M * N floats), then summed in a fixed order (deterministic).  splits == 1 -> one plain launch.
-extern "C" int lhrs_gemm_splitk_splits(int M, int N, int K) {
-  const long tiles = (long)cdiv(M, 128) * cdiv(N, 128);
-  long s = (512 + tiles / 2) / tiles;
-  if (s > K / 1024) s = K / 1024;
-  if (s > 8) s = 8;
-  return s < 1 ? 1 : (int)s;
-}
-
-extern "C" int lhrs_gemm_bf16_nt_splitk_f32(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K,
-                                            float* workspace, void* stream) {
-  LHRS_REQUIRE(M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 4 == 0 && ldc % 4 == 0 && ldc >= N && lda % 8 == 0 && ldb % 8 == 0 && lda >= K && ldb >= K,
-               "gemm_splitk_f32: M=%d N=%d K=%d lda=%d ldb=%d ldc=%d", M, N, K, lda, ldb, ldc);
-  const int splits = lhrs_gemm_splitk_splits(M, N, K);
-  if (splits == 1) return gemm_launch(A, lda, B, ldb, C, ldc, M, N, K, nullptr, nullptr, 0, 0, 1, 0, 1.f, nullptr, 0, nullptr, 0, 0, stream);
-  LHRS_REQUIRE(workspace != nullptr, "gemm_splitk_f32: %d splits need a workspace of splits * M * N floats", splits);
-  const int ks = cdiv(K / 64, splits) * 64;
-  GemmArgs g; memset(&g, 0, sizeof(g));
-  g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = workspace; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = N;
-  g.alpha = 1.f; g.out_f32 = 1; g.ksplit = ks;
-  g.tilesM = cdiv(M, 128); g.tilesN = cdiv(N, 128);
-  const int used = cdiv(K, ks);
-  hipStream_t s = (hipStream_t)stream;
-  if (g_prof.on) { g_prof.launches_all++; g_prof.total_flops_all += 2.0 * M * N * K; }
-  hipLaunchKernelGGL((gemm_nt_kernel<4, 4, 0>), dim3(g.tilesM * g.tilesN, used), dim3(256), 0, s, g);
-  LHRS_CHECK_LAUNCH("gemm_splitk_f32");
-  const long work = (long)M * (N / 4);
-  int rg = (int)((work + 255) / 256); if (rg > 8192) rg = 8192;
-  hipLaunchKernelGGL(splitk_reduce_f32_kernel, dim3(rg), dim3(256), 0, s, workspace, C, (long)ldc, M, N, used);
-  LHRS_CHECK_LAUNCH("gemm_splitk_f32 reduce");
   return 0;
 }

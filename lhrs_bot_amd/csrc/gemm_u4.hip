@@ -32,6 +32,7 @@
 // (gemm_nt_256s_kernel's staged epilogue rounds the sum first).  SwiGLU / RoPE epilogues round gate / up / d_act / q / k to bf16 exactly where the unfused kernel
 // pairs store them: bit-identical to those (tests/test_kernels_gpu.py).
 #include "common.h"
+#include "gemm_plan.h"
 #include "gemm_u4_agpr.inc"
 
 namespace {
@@ -455,21 +456,10 @@ __global__ __launch_bounds__(256, 1) void gemm_u4_kernel(U4Args g) {
 }
 }  // namespace
 
-static bool u4_addressable(const void* A, int lda, const void* B, int ldb, const void* C, int ldc, int M, int N, int K) {
-  return M > 0 && N > 0 && K >= 256 && K % 64 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && lda >= K && ldb >= K && ldc >= N &&
-         ((size_t)A | (size_t)B | (size_t)C) % 16 == 0 && (long)M * lda * 2 < (1L << 32) && (long)N * ldb * 2 < (1L << 32) &&      // 32-bit lane offsets of the operands
-         (long)144 * ldc * 2 < (1L << 32);                                                                                           // ... and of a tile's output rows
-}
-// the optional second operand pair (fused LoRA update): rows of A2 / B2 as the rows of A / B; K2 a multiple of 64.  false: not addressable by this kernel
+using namespace gemm_plan_h;   // the addressing predicates the wrappers decline by (u4_*_ok): the planner of gemm.hip asks the same ones up front
+
+// the optional second operand pair (fused LoRA update): rows of A2 / B2 as the rows of A / B; K2 a multiple of 64, 0 = none
 struct U4Pair { const void* A2; int lda2; const void* B2; int ldb2; int K2; };
-static bool u4_pair(U4Args& g, const U4Pair* p, int rowsB) {
-  if (p == nullptr || p->K2 == 0) return true;
-  if (p->K2 < 0 || p->K2 % 64 != 0 || p->A2 == nullptr || p->B2 == nullptr || p->lda2 % 8 != 0 || p->ldb2 % 8 != 0 || p->lda2 < p->K2 || p->ldb2 < p->K2 ||
-      ((size_t)p->A2 | (size_t)p->B2) % 16 != 0 || (long)g.M * p->lda2 * 2 >= (1L << 32) || (long)rowsB * p->ldb2 * 2 >= (1L << 32))
-    return false;
-  g.A2 = (const bf16_t*)p->A2; g.B2 = (const bf16_t*)p->B2; g.lda2 = p->lda2; g.ldb2 = p->ldb2; g.K2 = p->K2;
-  return true;
-}
 static dim3 u4_grid(const U4Args& g) {
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
@@ -479,14 +469,13 @@ static dim3 u4_grid(const U4Args& g) {
 }
 
 // 0 launched; 1 not this kernel's problem (the caller takes gemm.hip's kernels); -1 error.  Plain epilogue: bf16 out, optional bf16 residual.
-static int u4_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const void* residual, int ldr, const U4Pair* pair,
+static int u4_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const void* residual, int ldr, const U4Pair& pair,
                  void* stream) {
-  if (!u4_addressable(A, lda, B, ldb, C, ldc, M, N, K) || (residual != nullptr && (ldr % 8 != 0 || ldr < N || (size_t)residual % 16 != 0 || (long)144 * ldr * 2 >= (1L << 32))))
-    return 1;
+  if (!u4_nt_ok(A, lda, B, ldb, C, ldc, M, N, K, residual, ldr, pair.A2, pair.lda2, pair.B2, pair.ldb2, pair.K2)) return 1;
   U4Args g{};
   g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = (bf16_t*)C; g.res = (const bf16_t*)residual;
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr; g.tilesM = (M + 255) / 256; g.tilesN = (N + 255) / 256; g.rope_mod = 1;
-  if (!u4_pair(g, pair, N)) return 1;
+  if (pair.K2 != 0) { g.A2 = (const bf16_t*)pair.A2; g.B2 = (const bf16_t*)pair.B2; g.lda2 = pair.lda2; g.ldb2 = pair.ldb2; g.K2 = pair.K2; }
   if (residual != nullptr) hipLaunchKernelGGL((gemm_u4_kernel<0, true>), u4_grid(g), dim3(256), 0, (hipStream_t)stream, g);
   else hipLaunchKernelGGL((gemm_u4_kernel<0, false>), u4_grid(g), dim3(256), 0, (hipStream_t)stream, g);
   LHRS_CHECK_LAUNCH("gemm_u4_nt");
@@ -494,48 +483,42 @@ static int u4_nt(const void* A, int lda, const void* B, int ldb, void* C, int ld
 }
 extern "C" int lhrs_gemm_u4_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const void* residual, int ldr,
                                void* stream) {
-  return u4_nt(A, lda, B, ldb, C, ldc, M, N, K, residual, ldr, nullptr, stream);
+  return u4_nt(A, lda, B, ldb, C, ldc, M, N, K, residual, ldr, U4Pair{}, stream);
 }
 // ... + A2 . B2^T in the same k-loop (lhrs_gemm_bf16_nt_lora's semantics with a plain epilogue; bit-identical to the 16-wave kernel's fused pair)
 extern "C" int lhrs_gemm_u4_nt_lora(const void* A, int lda, const void* B, int ldb, const void* A2, int lda2, const void* B2, int ldb2, int K2, void* C, int ldc,
                                     int M, int N, int K, const void* residual, int ldr, void* stream) {
-  const U4Pair p{A2, lda2, B2, ldb2, K2};
-  return u4_nt(A, lda, B, ldb, C, ldc, M, N, K, residual, ldr, &p, stream);
+  return u4_nt(A, lda, B, ldb, C, ldc, M, N, K, residual, ldr, U4Pair{A2, lda2, B2, ldb2, K2}, stream);
 }
 
 // q|k|v projection with RoPE in the epilogue (the semantics of lhrs_gemm_rope_fwd without a LoRA pair): columns [0, rope_cols) are heads of 128 rotated with
 // the position m % pos_mod + pos0 of their row, the rest stored as computed.  0 launched; 1 not this kernel's problem.
 static int u4_rope(const void* X, int ldx, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const float* cos_t, const float* sin_t,
-                   int pos_mod, int pos0, int rope_cols, const U4Pair* pair, void* stream) {
-  if (!u4_addressable(X, ldx, W, ldw, C, ldc, M, N, K) || rope_cols % 256 != 0 || rope_cols > N || pos_mod < 16 || pos0 < 0 || cos_t == nullptr || sin_t == nullptr ||
-      ((size_t)cos_t | (size_t)sin_t) % 16 != 0 || (long)(pos_mod + pos0) * 64 * 4 >= (1L << 31))
-    return 1;
+                   int pos_mod, int pos0, int rope_cols, const U4Pair& pair, void* stream) {
+  if (!u4_rope_ok(X, ldx, W, ldw, C, ldc, M, N, K, cos_t, sin_t, pos_mod, pos0, rope_cols, pair.A2, pair.lda2, pair.B2, pair.ldb2, pair.K2)) return 1;
   U4Args g{};
   g.A = (const bf16_t*)X; g.B = (const bf16_t*)W; g.C = (bf16_t*)C; g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldb = ldw; g.ldc = ldc;
   g.tilesM = (M + 255) / 256; g.tilesN = (N + 255) / 256;
   g.rope_cos = cos_t; g.rope_sin = sin_t; g.rope_mod = pos_mod; g.rope_pos0 = pos0; g.rope_cols = rope_cols;
-  if (!u4_pair(g, pair, N)) return 1;
+  if (pair.K2 != 0) { g.A2 = (const bf16_t*)pair.A2; g.B2 = (const bf16_t*)pair.B2; g.lda2 = pair.lda2; g.ldb2 = pair.ldb2; g.K2 = pair.K2; }
   hipLaunchKernelGGL((gemm_u4_kernel<3, false>), u4_grid(g), dim3(256), 0, (hipStream_t)stream, g);
   LHRS_CHECK_LAUNCH("gemm_u4_rope");
   return 0;
 }
 extern "C" int lhrs_gemm_u4_rope(const void* X, int ldx, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const float* cos_t, const float* sin_t,
                                  int pos_mod, int pos0, int rope_cols, void* stream) {
-  return u4_rope(X, ldx, W, ldw, C, ldc, M, N, K, cos_t, sin_t, pos_mod, pos0, rope_cols, nullptr, stream);
+  return u4_rope(X, ldx, W, ldw, C, ldc, M, N, K, cos_t, sin_t, pos_mod, pos0, rope_cols, U4Pair{}, stream);
 }
 extern "C" int lhrs_gemm_u4_rope_lora(const void* X, int ldx, const void* W, int ldw, const void* A2, int lda2, const void* B2, int ldb2, int K2, void* C, int ldc,
                                       int M, int N, int K, const float* cos_t, const float* sin_t, int pos_mod, int pos0, int rope_cols, void* stream) {
-  const U4Pair p{A2, lda2, B2, ldb2, K2};
-  return u4_rope(X, ldx, W, ldw, C, ldc, M, N, K, cos_t, sin_t, pos_mod, pos0, rope_cols, &p, stream);
+  return u4_rope(X, ldx, W, ldw, C, ldc, M, N, K, cos_t, sin_t, pos_mod, pos0, rope_cols, U4Pair{A2, lda2, B2, ldb2, K2}, stream);
 }
 
 // LLaMA MLP, forward half: gu [M, 2 ff] = X . Wgu^T (Wgu = [gate; up] weight [2 ff, K]) and act [M, ff] = silu(gate) * up in one launch (the semantics of
 // lhrs_gemm_swiglu_fwd without a LoRA pair; bit-identical).  0 launched; 1 not this kernel's problem.
 extern "C" int lhrs_gemm_u4_swiglu_fwd(const void* X, int ldx, const void* Wgu, int ldw, void* gu, int ld_gu, void* act, int ld_act, int M, int ff, int K,
                                        void* stream) {
-  if (ff <= 0 || ff % 128 != 0 || !u4_addressable(X, ldx, Wgu, ldw, gu, ld_gu, M, 2 * ff, K) || ld_act % 8 != 0 || ld_act < ff || (size_t)act % 16 != 0 ||
-      (long)144 * ld_act * 2 >= (1L << 32) || (long)2 * ff * ldw * 2 >= (1L << 32))
-    return 1;
+  if (!u4_swiglu_fwd_ok(X, ldx, Wgu, ldw, gu, ld_gu, act, ld_act, M, ff, K)) return 1;
   U4Args g{};
   g.A = (const bf16_t*)X; g.B = (const bf16_t*)Wgu; g.C = (bf16_t*)gu; g.M = M; g.N = 2 * ff; g.K = K; g.lda = ldx; g.ldb = ldw; g.ldc = ld_gu;
   g.tilesM = (M + 255) / 256; g.tilesN = ff / 128; g.rope_mod = 1;
@@ -548,7 +531,7 @@ extern "C" int lhrs_gemm_u4_swiglu_fwd(const void* X, int ldx, const void* Wgu, 
 // LLaMA MLP, backward half: dgu [M, 2 ff] = swiglu'(gu) * (dY . WdT^T) in one launch (lhrs_gemm_swiglu_bwd without a LoRA pair; bit-identical); dgu may alias gu
 // (a lane reads the gate / up values of exactly the elements it overwrites, before it writes them).  0 launched; 1 not this kernel's problem.
 extern "C" int lhrs_gemm_u4_swiglu_bwd(const void* dY, int ldy, const void* WdT, int ldw, const void* gu, void* dgu, int ld_gu, int M, int ff, int K, void* stream) {
-  if (ff <= 0 || ff % 8 != 0 || !u4_addressable(dY, ldy, WdT, ldw, dgu, ld_gu, M, ff, K) || ld_gu < 2 * ff || ((size_t)gu) % 16 != 0) return 1;
+  if (!u4_swiglu_bwd_ok(dY, ldy, WdT, ldw, gu, dgu, ld_gu, M, ff, K)) return 1;
   U4Args g{};
   g.A = (const bf16_t*)dY; g.B = (const bf16_t*)WdT; g.C = (bf16_t*)dgu; g.M = M; g.N = ff; g.K = K; g.lda = ldy; g.ldb = ldw; g.ldc = ld_gu;
   g.tilesM = (M + 255) / 256; g.tilesN = (ff + 255) / 256; g.rope_mod = 1;

@@ -269,14 +269,14 @@ class Plan:
 
 
 def u4_takes(M, N, K, lda, ldb, ldc, ldr=0, bias=False, act=0, out_f32=False, accumulate=False, alpha=1.0, cus=256):
-    """lhrs_gemm_u4_takes (gemm.hip:1074)"""
+    """lhrs_gemm_u4_takes (gemm_plan.h: u4_takes)"""
     tiles = cdiv(M, 256) * cdiv(N, 256)
     return (not bias and act == 0 and not out_f32 and not accumulate and alpha == 1.0 and K >= 4096 and K % 64 == 0 and M >= 1024 and
             N >= 1024 and 5 * tiles >= 4 * cus and lda % 8 == 0 and ldb % 8 == 0 and ldc % 8 == 0 and ldr % 8 == 0)
 
 
 def u4_fused_takes(kind, M, tiles_n, K, K2, cus=256):
-    """lhrs_gemm_u4_fused_takes (gemm.hip:1090); kind 0 RoPE, 1 SwiGLU forward, 2 SwiGLU backward"""
+    """lhrs_gemm_u4_fused_takes (gemm_plan.h: u4_fused_takes); kind 0 RoPE, 1 SwiGLU forward, 2 SwiGLU backward"""
     T = cdiv(M, 256) * tiles_n
     R = (T + cus - 1) // cus * cus
     idle_ok = 100 * R <= 105 * T if kind == 2 else 20 * R <= 23 * T
@@ -284,7 +284,7 @@ def u4_fused_takes(kind, M, tiles_n, K, K2, cus=256):
 
 
 def u4_main_rows(M, tiles_n, cus=256):
-    """u4_main_rows (gemm.hip:1119)"""
+    """lhrs_gemm_u4_main_rows (gemm_plan.h: u4_main_rows)"""
     tm = cdiv(M, 256)
     T = tm * tiles_n
     full = T // cus
@@ -295,12 +295,12 @@ def u4_main_rows(M, tiles_n, cus=256):
 
 
 def swiglu_fusable(tiles, ff, K, K2, lda=8, ldb=8):
-    """swiglu_fusable (gemm.hip:1338)"""
+    """gemm_plan.h: swiglu_fusable"""
     return ff % 256 == 0 and K % 64 == 0 and K2 % 64 == 0 and K + K2 >= 128 and tiles >= 128 and lda % 8 == 0 and ldb % 8 == 0
 
 
 def pick_144(M, tiles_n, K, K2, drop, cus=256):
-    """pick_144 (gemm.hip:1007) at set_bm144(1)"""
+    """gemm_plan.h: pick_144 at set_bm144(1)"""
     if K2 > 0 or drop or K < 192:
         return False
     t256, t144 = cdiv(M, 256) * tiles_n, cdiv(M, 144) * tiles_n
@@ -312,8 +312,8 @@ def pick_144(M, tiles_n, K, K2, drop, cus=256):
 
 
 def _tail_split(M, tiles_n, cus, rounds_by_cus):
-    """The tail-row rule (gemm.hip:1258, 1386, 1618) -> main rows or None.  rounds_by_cus: the cost of the unsplit walk counts rounds of
-    num_cus() (gemm_launch) or of 256 (the SwiGLU and e4m3 copies)."""
+    """The tail-row rule (gemm_plan.h: tail_main_rows) -> main rows or None.  rounds_by_cus: the cost of the unsplit walk counts rounds of
+    the CU count (plan_rows: its unsplit_cus argument) or of 256 (the SwiGLU-forward and e4m3 callers)."""
     tm = cdiv(M, 256)
     T = tm * tiles_n
     full = T // 256
@@ -327,7 +327,7 @@ def _tail_split(M, tiles_n, cus, rounds_by_cus):
 
 
 def splitk_tail_splits(M_tail, N, K, cus=256, workspace=True):
-    """tail_rows_splitk (gemm.hip:1183): slab count, or 0 when it does not apply"""
+    """gemm_plan.h: splitk_tail_splits: slab count, or 0 when it does not apply"""
     splits = (K + 2048) // 4096 if K >= 8192 else 1
     if splits <= 1 or N % 128 != 0 or not workspace or splits * M_tail * N * 4 > cus * 256 * 256 * 4:
         return 0
@@ -336,7 +336,7 @@ def splitk_tail_splits(M_tail, N, K, cus=256, workspace=True):
 
 def _gemm_launch(P, r0, M, N, K, *, K2=0, bias=False, res=False, act=0, out_f32=False, accumulate=False, drop=False, ldc=None,
                  ldr=None, split_ok=True, cus=256, workspace=True):
-    """gemm_launch (gemm.hip:1204)"""
+    """gemm_plan.h: plan_rows"""
     ldc = N if ldc is None else ldc
     ldr = N if ldr is None else ldr
     t128, t64x128, t256 = cdiv(M, 128) * cdiv(N, 128), cdiv(M, 64) * cdiv(N, 128), cdiv(M, 256) * cdiv(N, 256)
@@ -425,7 +425,7 @@ def path_of(entry, M, N, K, *, K2=0, bias=False, res=False, act=0, out_f32=False
         else:
             P.add(0, M, "fp8_256")
     elif entry == "int8":
-        P.add(0, M, "i8_256")      # gemm_fp8_launch takes no tail split when i8: the small-tile sibling exists for e4m3 only
+        P.add(0, M, "i8_256")      # gemm_plan takes no tail split for int8: the small-tile sibling exists for e4m3 only
     elif entry == "splitk_f32":
         if splitk_splits(M, N, K) == 1:
             _gemm_launch(P, 0, M, N, K, out_f32=True, ldc=ldc, **kw)
@@ -437,7 +437,7 @@ def path_of(entry, M, N, K, *, K2=0, bias=False, res=False, act=0, out_f32=False
 
 
 def _swiglu_fwd(P, r0, M, ff, K, K2, ld_gu, ld_act, split_ok, cus, workspace):
-    """lhrs_gemm_swiglu_fwd (gemm.hip:1371)"""
+    """lhrs_gemm_swiglu_fwd (gemm_plan.h: plan_swiglu_fwd)"""
     if ff % 128 == 0 and u4_fused_takes(1, M, ff // 128, K, K2, cus):
         P.add(r0, r0 + M, "u4_swiglu_fwd", 7)
         return
@@ -455,18 +455,18 @@ def _swiglu_fwd(P, r0, M, ff, K, K2, ld_gu, ld_act, split_ok, cus, workspace):
 
 
 def splitk_splits(M, N, K):
-    """lhrs_gemm_splitk_splits (gemm.hip:1718)"""
+    """lhrs_gemm_splitk_splits (gemm_plan.h: splitk_f32_splits)"""
     tiles = cdiv(M, 128) * cdiv(N, 128)
     return max(1, min((512 + tiles // 2) // tiles, K // 1024, 8))
 
 
 def skinny_splits(K, N):
-    """lhrs_gemm_skinny_splits (gemm.hip:1684)"""
+    """lhrs_gemm_skinny_splits (gemm.hip)"""
     return max(1, min(K // 512, 16 if N <= 128 else 4))
 
 
 def tn_splits(T, Mo, No):
-    """lhrs_gemm_tn_splits (gemm_tn.hip:161), 64-token stages"""
+    """lhrs_gemm_tn_splits (gemm_tn.hip), 64-token stages"""
     tiles = (Mo // 128) * (No // 128)
     if tiles < 1 or T < 1:
         return 1
@@ -489,7 +489,7 @@ _LAUNCH_KERNELS = {"256", "144", "t128", "t64x128", "t64x64", "splitk_tail"}
 
 
 def cells_of(entry, kernels):
-    """{(entry, kernel)} of one path.  The unfused fallbacks of the SwiGLU and RoPE entry points run gemm_launch (whose kernels the 'nt' cells
+    """{(entry, kernel)} of one path.  The unfused fallbacks of the SwiGLU and RoPE entry points run the plain launcher (plan_rows, whose kernels the 'nt' cells
     cover) and an elementwise pass: one cell 'unfused' each."""
     if entry in ("swiglu_fwd", "swiglu_bwd", "rope"):
         return {(entry, "unfused" if k in _LAUNCH_KERNELS else k) for k in kernels}

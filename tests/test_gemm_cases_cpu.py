@@ -1,7 +1,9 @@
 """The tools of tests/gemm_cases.py on the CPU: the comparator rejects subtly wrong GEMM results (each mutation of a float64 reference
 by at least 3x its bound, while the reference rounded to the output type passes), the old whole-matrix rel-L2 check would not, and
 path_of's restated host rules agree with the ones the library exports."""
+import ctypes
 import math
+from collections import Counter
 
 import pytest
 import torch
@@ -266,6 +268,128 @@ def test_path_of_hand_worked_shapes():
     assert P("rope", 2184, 4096, 4096, rope_cols=2048).kernels() == ("rope_144",)
     assert P("fp8", 8736, 4096, 4096).segments == [(0, 8192, "fp8_256"), (8192, 8736, "fp8_small")]
     assert P("int8", 8736, 4096, 4096).segments == [(0, 8736, "i8_256")] and P("int8", 1, 8, 256).launches == 1   # no tail split for int8
+    assert P("splitk_f32", 2048, 1024, 27392).kernels() == ("splitk_f32",) and P("splitk_f32", 256, 128, 640).kernels() == ("t64x64",)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the library's planner
+# lhrs_gemm_plan (csrc/gemm_plan.h, the planner every GEMM entry point runs through) against path_of, which stays the reference.
+
+_ENTRY = {"nt": 0, "lora": 0, "mask": 0, "swiglu_fwd": 1, "swiglu_bwd": 2, "rope": 3, "fp8": 4, "int8": 5, "splitk_f32": 6}
+
+
+def lib_plan(lib, entry, Mv, Nv, Kv, *, K2=0, bias=False, res=False, act=0, out_f32=False, accumulate=False, alpha=1.0, ldc=None, ldr=None, ff=0,
+             rope_cols=0, head_dim=128, al16_ptrs=True, cus=256, workspace=True):
+    """lhrs_gemm_plan with path_of's arguments (dense operands but ldc and ldr) -> (segments, Counter of profile kinds, launches)"""
+    flags = 1 * bias | 2 * res | 4 * out_f32 | 8 * accumulate | 16 * (entry == "mask")
+    quads = (ctypes.c_int * 32)()
+    n = lib.lhrs_gemm_plan(_ENTRY[entry], Mv, Nv, Kv, K2, flags, act, alpha, Kv, Kv, Nv if ldc is None else ldc, Nv if ldr is None else ldr, ff, 2 * ff, ff, rope_cols, head_dim,
+                           16 if al16_ptrs else 8, cus, int(workspace), quads, 8)
+    assert 0 < n <= 8, (entry, Mv, Nv, Kv, n)
+    segments = [(quads[4 * i], quads[4 * i + 1], lib.lhrs_gemm_kernel_name(quads[4 * i + 2]).decode()) for i in range(n)]
+    return segments, Counter(quads[4 * i + 3] for i in range(n) if quads[4 * i + 3] >= 0), n
+
+
+def _same_plan(lib, entry, Mv, Nv, Kv, **kw):
+    want = gc.path_of(entry, Mv, Nv, Kv, **kw)
+    got = lib_plan(lib, entry, Mv, Nv, Kv, **kw)
+    assert got == (want.segments, want.kinds, want.launches), (entry, Mv, Nv, Kv, kw, got, want.segments, want.kinds)
+
+
+_NT_FLAGS = (("nt", {}), ("nt", dict(bias=True)), ("nt", dict(bias=True, act=1)), ("nt", dict(act=3)), ("nt", dict(res=True)), ("nt", dict(alpha=0.5)),
+             ("nt", dict(out_f32=True)), ("nt", dict(out_f32=True, accumulate=True)), ("lora", dict(K2=64)), ("lora", dict(K2=64, res=True)),
+             ("lora", dict(K2=64, out_f32=True)), ("mask", {}), ("mask", dict(res=True)))
+_FFS = (1000, 2048, 4096, 11008)
+
+
+@pytest.mark.parametrize("cus", [256, 304])
+@pytest.mark.parametrize("workspace", [True, False])
+def test_library_plan_equals_path_of(cus, workspace):
+    """Segments, profile kinds and launch count of lhrs_gemm_plan == path_of over SHAPES_M x SHAPES_N x SHAPES_K and every entry / flag combination
+    reachable_paths sweeps, on 256 and 304 CUs (where the CU-count and the 256-round copies of the tail-row rule differ), with and without a workspace."""
+    lib = _lib.load()
+    lib.lhrs_gemm_set_u4(1)
+    kw = dict(cus=cus, workspace=workspace)
+    for Mv in SHAPES_M:
+        for Nv in SHAPES_N:
+            for Kv in SHAPES_K:
+                for entry, f in _NT_FLAGS:
+                    _same_plan(lib, entry, Mv, Nv, Kv, **f, **kw)
+                _same_plan(lib, "nt", Mv, Nv, Kv, ldc=Nv + 8, **kw)                  # strided output (16-B rows when N % 8 == 0)
+                _same_plan(lib, "nt", Mv, Nv, Kv, res=True, ldc=Nv + 8, **kw)
+                for ldr in (Nv + 4, Nv + 8):                                         # residual rows that are / are not 16-B multiples
+                    _same_plan(lib, "nt", Mv, Nv, Kv, res=True, ldr=ldr, **kw)
+                    _same_plan(lib, "lora", Mv, Nv, Kv, K2=64, res=True, ldr=ldr, **kw)
+                for entry in ("fp8", "int8", "splitk_f32"):
+                    _same_plan(lib, entry, Mv, Nv, Kv, **kw)
+                for K2 in (0, 64):
+                    _same_plan(lib, "rope", Mv, Nv, Kv, K2=K2, rope_cols=Nv // 512 * 256, **kw)
+        for ff in _FFS:
+            for Kv in SHAPES_K:
+                for K2 in (0, 64):
+                    _same_plan(lib, "swiglu_fwd", Mv, 0, Kv, K2=K2, ff=ff, **kw)
+                    _same_plan(lib, "swiglu_bwd", Mv, 0, Kv, K2=K2, ff=ff, **kw)
+
+
+def test_library_plan_with_8_byte_aligned_operands(monkeypatch):
+    """Operands that are only 8-byte aligned never reach the four-wave kernel.  The plain entry points: path_of(al16_ptrs=False).  The fused ones
+    (path_of's flag covers the plain entries only): the plan the declining wrappers of gemm_u4.hip used to leave - path_of at the same shape with
+    its u4_fused_takes branch never taken."""
+    lib = _lib.load()
+    lib.lhrs_gemm_set_u4(1)
+    for Mv in SHAPES_M:
+        for Nv in SHAPES_N:
+            for Kv in SHAPES_K:
+                for entry, f in _NT_FLAGS:
+                    _same_plan(lib, entry, Mv, Nv, Kv, al16_ptrs=False, **f)
+    monkeypatch.setattr(gc, "u4_fused_takes", lambda *a, **k: False)
+    for Mv in SHAPES_M:
+        for Nv in SHAPES_N:
+            for Kv in SHAPES_K:
+                for K2 in (0, 64):
+                    _same_plan(lib, "rope", Mv, Nv, Kv, K2=K2, rope_cols=Nv // 512 * 256, al16_ptrs=False)
+        for ff in _FFS:
+            for Kv in SHAPES_K:
+                for entry in ("swiglu_fwd", "swiglu_bwd"):
+                    _same_plan(lib, entry, Mv, 0, Kv, ff=ff, al16_ptrs=False)
+
+
+def test_hand_worked_shapes_come_out_of_the_library():
+    """The expectations of test_path_of_hand_worked_shapes, verbatim, asked of lhrs_gemm_plan."""
+    lib = _lib.load()
+    lib.lhrs_gemm_set_u4(1)
+
+    class L:
+        def __init__(self, entry, Mv, Nv, Kv, **kw):
+            self.segments, self.kinds, self.launches = lib_plan(lib, entry, Mv, Nv, Kv, **kw)
+
+        def kernels(self):
+            return tuple(k for _, _, k in self.segments)
+
+    P = L
+    p = P("nt", 8736, 4096, 11008)
+    assert p.segments == [(0, 8192, "u4"), (8192, 8736, "splitk_tail")] and p.kinds == {6: 1} and p.launches == 2
+    p = P("nt", 8736, 4096, 4096)
+    assert p.segments == [(0, 8192, "u4"), (8192, 8736, "t64x128")] and p.launches == 2
+    p = P("lora", 8736, 4096, 4096, K2=64)
+    assert p.kernels() == ("u4", "t64x128", "t64x128") and p.launches == 3
+    assert P("nt", 3839, 4104, 4096, res=True, ldc=4112).kernels() == ("u4",)
+    assert P("nt", 4000, 4096, 1024, bias=True, act=1).kernels() == ("256",)
+    assert P("nt", 8736, 4096, 4096, bias=True).segments == [(0, 8192, "256"), (8192, 8736, "t64x128")]
+    assert P("nt", 2184, 4096, 4096, act=2, bias=True).kernels() == ("144",)
+    assert P("nt", 7710, 1024, 1024, bias=True, res=True).kernels() == ("144",)
+    assert P("nt", 3000, 2048, 512).kernels() == ("t128",) and P("nt", 2000, 1024, 256).kernels() == ("t64x128",)
+    assert P("nt", 300, 264, 320).kernels() == ("t64x64",)
+    assert P("nt", 8190, 4100, 4096).kernels() == ("t128",)
+    assert P("nt", 8190, 4096, 4096, al16_ptrs=False).kernels() == ("256",)
+    assert P("mask", 4096, 4096, 128).kernels() == ("256",) and P("mask", 300, 4096, 64).kernels() == ("t64x64",)
+    assert P("swiglu_fwd", 4000, 0, 4096, ff=2048).kernels() == ("u4_swiglu_fwd",)
+    assert P("swiglu_fwd", 2184, 0, 4096, ff=11008).segments == [(0, 2048, "u4_swiglu_fwd"), (2048, 2184, "t64x128")]
+    assert P("swiglu_fwd", 300, 0, 256, ff=1000).kernels() == ("t64x64",)
+    assert P("swiglu_bwd", 4096, 0, 4096, ff=4096).kernels() == ("u4_swiglu_bwd",)
+    assert P("rope", 4000, 4096, 4096, rope_cols=2048).kernels() == ("u4_rope",)
+    assert P("rope", 2184, 4096, 4096, rope_cols=2048).kernels() == ("rope_144",)
+    assert P("fp8", 8736, 4096, 4096).segments == [(0, 8192, "fp8_256"), (8192, 8736, "fp8_small")]
+    assert P("int8", 8736, 4096, 4096).segments == [(0, 8736, "i8_256")] and P("int8", 1, 8, 256).launches == 1
     assert P("splitk_f32", 2048, 1024, 27392).kernels() == ("splitk_f32",) and P("splitk_f32", 256, 128, 640).kernels() == ("t64x64",)
 
 

@@ -6,8 +6,8 @@ Inputs are poisoned: NaN in the padding columns [K, lda) of A, B, A2, B2, in the
 cos / sin rows past the last position used (e4m3 operands: NaN bytes past K).  Outputs are [M + 3, ldc > N] buffers prefilled with a sentinel bit pattern; everything outside [0, M) x [0, N)
 must come back unchanged.  Every term of a result (pair, bias, residual, mask, RoPE, accumulated C) carries at least ~5 % of its RMS.
 
-8-byte aligned operands (column-offset views): lhrs_gemm_bf16_nt accepts them (it checks lda % 8), the four-wave kernel declines them
-(plain_u4_try) and the 16-wave, 144-row and small-tile kernels move their rows with 16-byte global_load_lds_dwordx4 and 16-byte stores.
+8-byte aligned operands (column-offset views): lhrs_gemm_bf16_nt accepts them (it checks lda % 8), the four-wave kernel is not planned for them
+(gemm_plan.h: u4_nt_ok) and the 16-wave, 144-row and small-tile kernels move their rows with 16-byte global_load_lds_dwordx4 and 16-byte stores.
 gfx950 supports unaligned global (buffer) loads and stores - the compiler's own gfx950 target lists unaligned-buffer-access and emits
 global_load_dwordx4 / global_store_dwordx4 for 8-byte aligned vectors - and the LDS side of the DMA is the wave's aligned LDS base + 16 x
 lane, independent of the global address; so the cases below run such views like any other."""

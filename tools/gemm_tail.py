@@ -1,4 +1,4 @@
-"""Tail-row rule of gemm_launch: the same product with and without the cut, on micro-batch-32 shapes (M = 32 * 273 = 8736)."""
+"""Tail-row rule (gemm_plan.h: tail_main_rows in plan_rows): the same product with and without the cut, on micro-batch-32 shapes (M = 32 * 273 = 8736)."""
 import os as _os
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
