@@ -351,7 +351,8 @@ def check_constraint(m, constraint, return_choices=False, do_sample=False, num_b
 def layer_step(m, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None, int8=False, scratch=None):
     """One decoder layer over S_new new positions per sequence behind `ctx` cached ones (prefill: ctx = 0).  li = the layer's index, under
     adapters="live" or int8: the linears are the training forward's (`_lin` / `_gu_fwd`; dropout is off) - adapters on the bf16 base weights,
-    or with int8 (weights="int8" only) `hk.int8_linear` on the int8 rows with the adapters of a live store on top.
+    or with int8 (weights="int8" only) `hk.int8_linear` on the int8 rows with the adapters of a live store on top.  Which of the two `_lin`
+    runs is the model's scheme (`m.base`: generate() has put the bf16 one in unless weights="int8"); `int8` is the caller's word for it.
 
     The e4m3 cache (four tensors) behind a context, ctx > 0 (generate(prefix_cache=...)): `scratch` = two bf16 tensors [B * (ctx + S_new), d]
     of the caller (`gemm_logits` makes them once for all layers).  The `ctx` cached K / V rows are dequantised into them
@@ -360,12 +361,12 @@ def layer_step(m, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None
     OTHER in exact bf16, as the positions of any prompt do, and the cached positions THROUGH THE CODES, as the single-token step does."""
     d, H, hd, ff = m.d, m.heads, m.hd, m.ff
     M = x.shape[0]
-    i8 = (lambda name: (L[name + "i8"], L[name + "i8s"])) if int8 else (lambda name: None)
+    assert li is None or int8 == m.base_int8, "layer_step(int8=...) and the model's base scheme disagree"
     h = hk.rmsnorm_fwd(x, L["ln1_w"], m.eps)
     if li is None:
         qkv = hk.gemm_rope_fwd(h, L["qkv_w"], m.cos, m.sin, pos_mod=S_new, pos0=ctx, rope_cols=2 * d, head_dim=hd)
     else:
-        qkv = m._lin(li, "qkv", h, L["qkv_w"], rope=(S_new, ctx), i8=i8("qkv_w"))
+        qkv = m._lin(li, "qkv", h, L, rope=(S_new, ctx))
     o = torch.empty((M, d), device=m.device, dtype=torch.bfloat16)
     if len(cache) == 4:
         # kv_cache="fp8", prefill: attention reads the exact bf16 K / V of the prompt straight out of `qkv` (desc: kv_off = b * S_new),
@@ -399,10 +400,10 @@ def layer_step(m, L, x, B, S_new, ctx, cache, desc, max_ctx, kmask=None, li=None
             hk.copy_2d(vc.data_ptr() + (b * max_ctx + ctx) * row_b, row_b, src + 2 * row_b, 3 * row_b, row_b, S_new)
         hk.attn_fwd(qkv[:, :d], kc, vc, o, None, desc, B, H, hd, S_new, 1 << 30, hk.pad64(S_new), True, 1.0 / math.sqrt(hd), key_mask=kmask)
     if li is not None:   # the fused gate|up + SwiGLU GEMM of the training forward; the arm below runs gemm_nt + swiglu_fwd (different kernels)
-        x = m._lin(li, "o", o, L["o_w"], residual=x, i8=i8("o_w"))
+        x = m._lin(li, "o", o, L, residual=x)
         h = hk.rmsnorm_fwd(x, L["ln2_w"], m.eps, out=h)
-        _, act, _ = m._gu_fwd(li, h, L["gu_w"], None, i8=i8("gu_w"))
-        return m._lin(li, "down", act, L["down_w"], residual=x, i8=i8("down_w"))
+        _, act, _ = m._gu_fwd(li, h, L, None)
+        return m._lin(li, "down", act, L, residual=x)
     x = hk.gemm_nt(o, L["o_w"], residual=x)
     h = hk.rmsnorm_fwd(x, L["ln2_w"], m.eps, out=h)
     act = hk.swiglu_fwd(hk.gemm_nt(h, L["gu_w"]), ff)

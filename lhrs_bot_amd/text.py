@@ -10,6 +10,7 @@ Activation memory per layer and token: x_in, x_mid, o (3 x 4096), qkv (12288), g
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import types
@@ -18,6 +19,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import generation, kernels as hk
+from .base_scheme import Bf16Base, E4m3Base, Int8Base
 from .generation import warp_logits  # noqa: F401  (callers import it from here)
 
 IGNORE_INDEX = -100
@@ -197,10 +199,8 @@ class TextModal:
         self.sin = fr.sin().to(torch.bfloat16).float().to(self.device).contiguous()
         self._ctx = None
         self.lora: Optional[LoraStore] = None
-        self.base8 = False  # frozen decoder linears in e4m3 (quantize_base(8, "e4m3"))
-        self.base_int8 = False  # frozen decoder linears as LLM.int8 (quantize_base(8, "int8"): the reference's bitsandbytes arithmetic)
-        self.base4 = None  # (quant_type, double_quant) once the decoder linears are bitsandbytes 4-bit storage (quantize_base(4, ...))
-        self._i8ws = None
+        self.base = Bf16Base()  # arithmetic of the frozen decoder linears (base_scheme.py); quantize_base installs another
+        self._merged_cache = None
         # training forward: run the last decoder layer's post-attention half on the supervised rows only when they are one contiguous
         # range per sequence (_layer_fwd `tail`); LHRS_TAIL_ROWS_ONLY=0 / attribute False: every row, as HF does
         self.tail_rows_only = os.environ.get("LHRS_TAIL_ROWS_ONLY", "1") != "0"
@@ -208,6 +208,12 @@ class TextModal:
 
     def get_text_encoder(self):
         return self
+
+    # read-only views of `self.base` (what the entry scripts, generation.py and the tests ask)
+    base8 = property(lambda self: isinstance(self.base, E4m3Base))      # frozen decoder linears in e4m3 (quantize_base(8, "e4m3"))
+    base_int8 = property(lambda self: isinstance(self.base, Int8Base))  # ... as LLM.int8 (quantize_base(8, "int8"): the reference's bitsandbytes arithmetic)
+    base4 = property(lambda self: self.base.storage4)  # (quant_type, double_quant) once they are bitsandbytes 4-bit storage (quantize_base(4, ...))
+    _i8ws = property(lambda self: self.base.ws)
 
     # ------------------------------------------------------------------ parameters
     def _finish(self):
@@ -249,15 +255,9 @@ class TextModal:
                 hk.gemm_nt(lo.derived[(li, gname, "Bfull")], lo.derived[(li, gname, "AT")], out=W, residual=W, alpha=lo.s)
                 L[gname + "_w" + "T"] = hk.transpose(W)
             self._drop_derived(L)
-        requant = "e4m3" if self.base8 else ("int8" if self.base_int8 else None)
-        base4 = getattr(self, "base4", None)
-        self.lora, self._merged_cache, self.base8, self.base_int8 = None, None, False, False
-        if requant:
-            self.quantize_base(8, requant)   # the 8-bit base is a function of the (now merged) weights
-        elif base4:
-            self.quantize_base(4, quant_type=base4[0], double_quant=base4[1])   # peft re-quantises a merged Linear4bit the same way
+        self.lora, self._merged_cache = None, None
+        self.base.install(self)   # the stored copies (8-bit operands, 4-bit states) are a function of the (now merged) weights
 
-    _W4_PARTS = {"qkv_w": 3, "o_w": 1, "gu_w": 2, "down_w": 1}   # reference Linears per fused weight (row-concatenated): 4-bit statistics are per Linear
     # rebuilt from a weight `<name>` / `<name>T`: the decode operands of generation.FORMATS + e4m3 copies, int8 rows and factors, 4-bit states
     DERIVED_SUFFIXES = generation.DECODE_SUFFIXES + ("8", "8s", "i8", "i8s", "q4")
 
@@ -302,115 +302,53 @@ class TextModal:
         seed = rec.get("seed_" + gname)
         return None if seed is None else (self.lora.dropout, seed)
 
-    def _q8(self, L, name):
-        """(e4m3 weight, per-row scales) of L[name] when the base weights are 8-bit (quantize_base), else None."""
-        return (L[name + "8"], L[name + "8s"]) if self.base8 else None
+    def _has(self, gname) -> bool:
+        return self.lora is not None and gname in self.lora.groups
 
-    def _i8(self, L, name):
-        """(int8 rows, dequantisation factors) of a decoder weight under the LLM.int8 base, else None"""
-        return (L[name + "i8"], L[name + "i8s"]) if self.base_int8 else None
-
-    def _lin(self, li, gname, x, W, residual=None, save=None, q8=None, xq=None, rope=None, i8=None):
-        """y = x W^T (+ s (x A^T) B^T when the group carries adapters) (+ residual).  q8 = (W8, scales): the frozen base product runs
-        on the e4m3 MFMA path (x quantised per row on the fly), the adapter update stays bf16 and rides on the same accumulators (lhrs_gemm_fp8_nt_lora).
-        rope = (pos_mod, pos0): the qkv projection - RoPE of the q / k heads in the bf16 GEMM's epilogue, a separate launch after the e4m3 one."""
+    def _adapter_down(self, li, gname, x, save):
+        """-> (T, Bfull), the adapter pair of the group's forward product: T [M, KP] = s * dropout(x) A^T; (None, None) without adapters.
+        T and the dropout seed go into `save` for the backward."""
         lo = self.lora
-        has_lora = lo is not None and gname in lo.groups
-        if has_lora:
-            xa, pd = x, lo.active_dropout()
-            if pd > 0:  # lora_A(dropout(x)): the mask is regenerated from the saved seed in the backward
-                seed = lo.seed_for(li, gname)
-                xa = hk.dropout(x, pd, seed)
-                if save is not None:
-                    save["seed_" + gname] = seed
-            T = hk.gemm_nt_skinny(xa, lo.view(lo.shadow, li, gname, "A"), alpha=lo.s)          # [M, KP] = s * dropout(x) A^T
+        if lo is None or gname not in lo.groups:
+            return None, None
+        xa, pd = x, lo.active_dropout()
+        if pd > 0:  # lora_A(dropout(x)): the mask is regenerated from the saved seed in the backward
+            seed = lo.seed_for(li, gname)
+            xa = hk.dropout(x, pd, seed)
             if save is not None:
-                save["T_" + gname] = T
-        if i8 is not None:  # LLM.int8 base (text_modal.py:91-131 -> bitsandbytes MatMul8bitLt): int8 product + 16-bit outlier columns, adapters on top
-            y = hk.int8_linear(x, i8[0], i8[1], self._i8ws, residual=residual, a2=T if has_lora else None,
-                               b2=lo.derived[(li, gname, "Bfull")] if has_lora else None)
-            if rope is not None:
-                hk.rope_(y, y.shape[0], 2 * self.heads, self.hd, self.cos, self.sin, pos_mod=rope[0], pos0=rope[1])
-            return y
-        if q8 is not None:
-            x8, sx = xq if xq is not None else hk.quant_fp8_rows(x)  # xq: the producer already emitted the e4m3 operand
-            if has_lora:
-                y = hk.gemm_fp8_nt(x8, sx, q8[0], q8[1], residual=residual, a2=T, b2=lo.derived[(li, gname, "Bfull")])
-            else:
-                y = hk.gemm_fp8_nt(x8, sx, q8[0], q8[1], residual=residual)
-            if rope is not None:
-                hk.rope_(y, y.shape[0], 2 * self.heads, self.hd, self.cos, self.sin, pos_mod=rope[0], pos0=rope[1])
-            return y
-        if rope is not None:
-            return hk.gemm_rope_fwd(x, W, self.cos, self.sin, pos_mod=rope[0], pos0=rope[1], rope_cols=2 * self.d, head_dim=self.hd,
-                                    a2=T if has_lora else None, b2=lo.derived[(li, gname, "Bfull")] if has_lora else None)
-        if not has_lora:
-            return hk.gemm_nt(x, W, residual=residual)
-        return hk.gemm_nt_lora(x, W, T, lo.derived[(li, gname, "Bfull")], residual=residual)
-
-    def _gu_fwd(self, li, h, W, save, q8=None, xq=None, i8=None):
-        """gate|up projection with the SwiGLU in the GEMM epilogue (one launch): -> (gu [M, 2ff], act [M, ff])."""
-        lo = self.lora
-        if i8 is not None:
-            gu = self._lin(li, "gu", h, W, save=save, i8=i8)
-            return gu, hk.swiglu_fwd(gu, self.ff), None
-        if self.base8:  # SwiGLU emits the e4m3 operand of the down projection; bf16 act only if an adapter on `down` needs it
-            gu = self._lin(li, "gu", h, W, save=save, q8=q8, xq=xq)
-            act, act8, sact = hk.swiglu_fwd_q(gu, self.ff, want_bf16=lo is not None and "down" in lo.groups)
-            return gu, act, (act8, sact)
-        if lo is None or "gu" not in lo.groups:
-            return hk.gemm_swiglu_fwd(h, W, self.ff) + (None,)
-        ha, pd = h, lo.active_dropout()
-        if pd > 0:
-            seed = lo.seed_for(li, "gu")
-            ha = hk.dropout(h, pd, seed)
-            if save is not None:
-                save["seed_gu"] = seed
-        T = hk.gemm_nt_skinny(ha, lo.view(lo.shadow, li, "gu", "A"), alpha=lo.s)
+                save["seed_" + gname] = seed
+        T = hk.gemm_nt_skinny(xa, lo.view(lo.shadow, li, gname, "A"), alpha=lo.s)
         if save is not None:
-            save["T_gu"] = T
-        return hk.gemm_swiglu_fwd(h, W, self.ff, T, lo.derived[(li, "gu", "Bfull")]) + (None,)
+            save["T_" + gname] = T
+        return T, lo.derived[(li, gname, "Bfull")]
 
-    def _down_bwd(self, li, dy, WT, gu, act, T, q8=None, dyq=None, drop=None):
-        """dgu (written over gu) = swiglu'(gu) * d_act with d_act = dy W_down (+ LoRA) never leaving the GEMM epilogue."""
-        lo = self.lora
-        if drop is not None and q8 is None:  # masked adapter term: unfused sequence
-            return hk.swiglu_bwd(self._lin_bwd(li, "down", dy, WT, act, T, drop=drop), gu, self.ff, out=gu)
-        if q8 is not None:  # -> (d(gate|up) bf16 over gu or None, its e4m3 operand for the gate|up dX product)
-            dact = self._lin_bwd(li, "down", dy, WT, act, T, q8=q8, dyq=dyq, drop=drop)
-            dgu, dgu8, sdgu = hk.swiglu_bwd_q(dact, gu, self.ff, want_bf16=lo is not None and "gu" in lo.groups)
-            return dgu, (dgu8, sdgu)
-        if lo is None or "down" not in lo.groups:
-            return hk.gemm_swiglu_bwd(dy, WT, gu, self.ff)
-        G = lo.groups["down"]
-        U = hk.gemm_nt_skinny(dy, lo.view(lo.shadow, li, "down", "BD"), alpha=lo.s)
-        dgu = hk.gemm_swiglu_bwd(dy, WT, gu, self.ff, U, lo.derived[(li, "down", "AT")])
-        hk.gemm_tn_skinny(U, act, lo.view(lo.grad, li, "down", "A"))
-        dBD = hk.gemm_tn_skinny(T, dy, lo.view(lo.grad, li, "down", "BD"))
-        hk.blockdiag_mask(dBD, lo.r, G["fout"], G["mask"])
-        return dgu
+    def _lin(self, li, gname, x, L, residual=None, save=None, xq=None, rope=None):
+        """y = x W^T (+ s (x A^T) B^T when the group carries adapters) (+ residual), W = L[gname + "_w"] in the arithmetic of `self.base`; the
+        adapter update stays bf16 and rides on the same accumulators.  xq: the producer already emitted the 8-bit operand of x.
+        rope = (pos_mod, pos0): the qkv projection - RoPE of the q / k heads."""
+        T, Bfull = self._adapter_down(li, gname, x, save)
+        return self.base.product(self, L, gname + "_w", x, xq, residual, T, Bfull, rope)
 
-    def _lin_bwd(self, li, gname, dy, WT, x, T, q8=None, dyq=None, drop=None):
-        """dx = dy W (+ s (dy B) A); adapter gradients dA = (s dy B)^T x, dB^T = (s x A^T)^T dy written into lora.grad.
-        q8 = (WT8, scales): e4m3 copy of the transposed base weight (per in-feature scales), dy quantised per row on the fly."""
-        lo = self.lora
-        has_lora = lo is not None and gname in lo.groups
-        if q8 is not None:
-            dy8, sdy = dyq if dyq is not None else hk.quant_fp8_rows(dy)
-            if not has_lora:
-                return hk.gemm_fp8_nt(dy8, sdy, q8[0], q8[1])
-        elif not has_lora:
-            return hk.gemm_nt(dy, WT)
+    def _gu_fwd(self, li, h, L, save, xq=None):
+        """gate|up projection + SwiGLU -> (gu [M, 2ff], act [M, ff] or None, 8-bit operand of act or None)"""
+        return self.base.gu_fwd(self, li, h, xq, L, save)
+
+    def _down_bwd(self, li, dy, L, gu, act, T, dyq=None, drop=None):
+        """-> (dgu = swiglu'(gu) * d_act, written over gu, or None; its 8-bit operand for the gate|up dX product or None), d_act = dy W_down (+ LoRA)"""
+        return self.base.down_bwd(self, li, dy, dyq, L, gu, act, T, drop)
+
+    def _lin_bwd(self, li, gname, dy, L, x, T, dyq=None, drop=None, **fused):
+        """dx = dy W (+ s (dy B) A), W^T = L[gname + "_wT"]; adapter gradients dA = (s dy B)^T x, dB^T = (s x A^T)^T dy written into lora.grad.
+        dyq: the producer's 8-bit operand of dy; drop = `_drop` of the forward; fused: see Bf16Base._dx."""
+        lo, base, name = self.lora, self.base, gname + "_wT"
+        dyq = base.operand(dy, dyq)
+        if lo is None or gname not in lo.groups:
+            return base.dx(L, name, dy, dyq, **fused)
         G = lo.groups[gname]
         U = hk.gemm_nt_skinny(dy, lo.view(lo.shadow, li, gname, "BD"), alpha=lo.s)         # [M, KP] = s * dy B
-        if drop is not None:  # dx = dy W + mask * (U A) / (1 - p): the adapter term cannot share the base product's accumulators
-            base = hk.gemm_fp8_nt(dy8, sdy, q8[0], q8[1]) if q8 is not None else hk.gemm_nt(dy, WT)
-            dx = hk.gemm_nt_dropmask(U, lo.derived[(li, gname, "AT")], drop[0], drop[1], residual=base)
+        dx = base.dx(L, name, dy, dyq, U, lo.derived[(li, gname, "AT")], drop, **fused)
+        if drop is not None:
             x = hk.dropout(x, drop[0], drop[1])                                            # dA sees the same masked input
-        elif q8 is not None:
-            dx = hk.gemm_fp8_nt(dy8, sdy, q8[0], q8[1], a2=U, b2=lo.derived[(li, gname, "AT")])
-        else:
-            dx = hk.gemm_nt_lora(dy, WT, U, lo.derived[(li, gname, "AT")])
         hk.gemm_tn_skinny(U, x, lo.view(lo.grad, li, gname, "A"))
         dBD = hk.gemm_tn_skinny(T, dy, lo.view(lo.grad, li, gname, "BD"))
         hk.blockdiag_mask(dBD, lo.r, G["fout"], G["mask"])
@@ -458,13 +396,9 @@ class TextModal:
                 save.append(rec)
             return x_out
         rec = {} if save is not None else None
-        lo = self.lora
-        hq = None
-        if self.base8:  # RMSNorm emits the e4m3 operand of the next GEMM; the bf16 copy only if an adapter reads it
-            h, hq = hk.rmsnorm_fwd_q(x, L["ln1_w"], self.eps, want_bf16=lo is not None and "qkv" in lo.groups)
-        else:
-            h = hk.rmsnorm_fwd(x, L["ln1_w"], self.eps)
-        qkv = self._lin(li, "qkv", h, L["qkv_w"], save=rec, q8=self._q8(L, "qkv_w"), xq=hq, rope=(S, 0), i8=self._i8(L, "qkv_w"))
+        base = self.base  # its norms and SwiGLU hand the 8-bit operand of the next product on (hq, actq; None in bf16)
+        h, hq = base.norm_fwd(x, L["ln1_w"], self.eps, self._has("qkv"))
+        qkv = self._lin(li, "qkv", h, L, save=rec, xq=hq, rope=(S, 0))
         o = torch.empty((M, d), device=self.device, dtype=torch.bfloat16)
         lse = torch.empty((B, H, LT), device=self.device, dtype=torch.float32)
         o_full, x_res = o, x
@@ -474,13 +408,10 @@ class TextModal:
             rows, tdesc, max_q = tail
             hk.attn_fwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, lse, tdesc, B, H, hd, max_q, S, LT, True, 1.0 / math.sqrt(hd))
             o, x_res = hk.gather_rows(o_full, rows), hk.gather_rows(x, rows)   # from here on: n rows
-        x_mid = self._lin(li, "o", o, L["o_w"], residual=x_res, save=rec, q8=self._q8(L, "o_w"), i8=self._i8(L, "o_w"))
-        if self.base8:
-            h, hq = hk.rmsnorm_fwd_q(x_mid, L["ln2_w"], self.eps, want_bf16=lo is not None and "gu" in lo.groups)
-        else:
-            h = hk.rmsnorm_fwd(x_mid, L["ln2_w"], self.eps, out=h if tail is None else None)
-        gu, act, actq = self._gu_fwd(li, h, L["gu_w"], rec, q8=self._q8(L, "gu_w"), xq=hq, i8=self._i8(L, "gu_w"))
-        x_out = self._lin(li, "down", act, L["down_w"], residual=x_mid, save=rec, q8=self._q8(L, "down_w"), xq=actq, i8=self._i8(L, "down_w"))
+        x_mid = self._lin(li, "o", o, L, residual=x_res, save=rec)
+        h, hq = base.norm_fwd(x_mid, L["ln2_w"], self.eps, self._has("gu"), out=h if tail is None else None)
+        gu, act, actq = self._gu_fwd(li, h, L, rec, xq=hq)
+        x_out = self._lin(li, "down", act, L, residual=x_mid, save=rec, xq=actq)
         if save is not None:
             rec.update(x_in=x, qkv=qkv, o=o, o_full=o_full, lse=lse, x_mid=x_mid, gu=gu)
             save.append(rec)
@@ -489,8 +420,7 @@ class TextModal:
     def _native_layer(self, tail) -> bool:
         """True when a decoder layer can go through the module-level entry points (lhrs_llama_layer_forward / _backward): the frozen bf16
         base without adapters, on every row (the compact last layer keeps the operator path).  LHRS_NATIVE_LAYER=0: operator path (A/B, tests)."""
-        return (tail is None and self.lora is None and not self.base8 and not self.base_int8 and self.hd == 128
-                and os.environ.get("LHRS_NATIVE_LAYER", "1") != "0")
+        return tail is None and self.lora is None and self.base.native_layer and self.hd == 128 and os.environ.get("LHRS_NATIVE_LAYER", "1") != "0"
 
     def forward_hidden(self, embeds, mask_u8, save_ctx=True, kv_len=None, tail=None):
         """embeds [B,S,d] bf16, mask [B,S] uint8 (right padding) -> final-norm hidden [B*S, d].  kv_len: the per-sequence key counts when
@@ -793,44 +723,15 @@ class TextModal:
         bf16 kernels then run the arithmetic bitsandbytes runs.  Parity: oracle/nf4_oracle.py (unpinned against the package)."""
         self._merged_cache = None     # generate() must not answer from pre-quantisation merged weights
         if bits == 4:
-            for L in self.p["layers"]:
-                self._drop_derived(L)
-                for k, parts in self._W4_PARTS.items():
-                    W = L[k]
-                    rows = W.shape[0] // parts
-                    states = []
-                    for i in range(parts):
-                        sub = W[i * rows:(i + 1) * rows]
-                        st = hk.quant4_blocks(sub, quant_type, double_quant)
-                        hk.dequant4_blocks(st, out=sub)              # from here on the 16-bit weight IS the 4-bit one
-                        states.append(st)
-                    L[k + "q4"] = states
-                    L[k + "T"] = hk.transpose(W)
-            self.base8, self.base_int8, self.base4 = False, False, (quant_type, bool(double_quant))
-            return self
-        if bits not in (8, 16):
+            base = Bf16Base(storage4=(quant_type, bool(double_quant)))
+        elif bits not in (8, 16):
             raise NotImplementedError(f"bits={bits}: 16 (bf16), 8 (LLM.int8 / e4m3 base weights) or 4 (nf4 / fp4 storage)")
-        if scheme not in ("e4m3", "int8"):
+        elif scheme not in ("e4m3", "int8"):
             raise ValueError(f"quantize_base scheme {scheme!r}: 'int8' (LLM.int8, the reference's) or 'e4m3'")
-        self.base4 = None
-        if bits == 16:
-            self.base8 = self.base_int8 = False
-            return self
-        if scheme == "int8":
-            for L in self.p["layers"]:
-                self._drop_derived(L)
-                for k in ("qkv_w", "o_w", "gu_w", "down_w"):
-                    L[k + "i8"], L[k + "i8s"] = hk.quant_int8_rows(L[k])
-                    hk.dequant_int8_rows(L[k + "i8"], L[k + "i8s"], out=L[k])     # from here on the 16-bit weight IS the int8 one
-                    L[k + "T"] = hk.transpose(L[k])
-            self._i8ws = hk.Int8Workspace(self.device, kmax=max(self.d, self.ff))
-            self.base8, self.base_int8 = False, True
-            return self
-        self.quantize_fp8()
-        for L in self.p["layers"]:
-            for k in ("qkv_wT", "o_wT", "gu_wT", "down_wT"):
-                L[k + "8"], L[k + "8s"] = hk.quant_fp8_rows(L[k])
-        self.base8, self.base_int8 = True, False
+        else:
+            base = Bf16Base() if bits == 16 else Int8Base() if scheme == "int8" else E4m3Base()
+        base.install(self)
+        self.base = base
         return self
 
     def _lora_merged_layers(self):
@@ -838,7 +739,7 @@ class TextModal:
         adapters.  Cached together with the decode re-tilings / e4m3 copies that `_decode_session` hangs onto the dicts, keyed on the adapter
         store's `version` (bumped by every optimizer step and load): an evaluation loop between two optimizer steps merges ONCE."""
         lo = self.lora
-        cache = getattr(self, "_merged_cache", None)
+        cache = self._merged_cache
         if cache is not None and cache[0] == (id(lo), lo.version):
             return cache[1]
         out = []
@@ -850,6 +751,21 @@ class TextModal:
             out.append(M)
         self._merged_cache = ((id(lo), lo.version), out)
         return out
+
+    @contextlib.contextmanager
+    def _decoding_on(self, weights, layers=None):
+        """generate() with un-merged adapters: the GEMM steps (prefill, batch > 16) run `_lin` / `_gu_fwd` on the bf16 weights - the 4-bit
+        storage keeps its name, `weights="int8"` keeps the LLM.int8 base it streams - and on `layers` (merged copies) when given.  The model's
+        own scheme and layers come back however the call ends."""
+        saved = self.base, self.p["layers"]
+        if not generation.int8_gemm(weights):
+            self.base = Bf16Base(self.base.storage4)
+        if layers is not None:
+            self.p["layers"] = layers
+        try:
+            yield
+        finally:
+            self.base, self.p["layers"] = saved
 
     @torch.no_grad()
     def generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p="default",
@@ -933,12 +849,12 @@ class TextModal:
             return self._generate(input_ids, **kw)
         if adapters == "live":   # nothing is merged or swapped: the bf16 base weights serve prefill, `weights` picks the decode stream, dropout is off
             lo = self.lora
-            saved = lo.train_mode, self.base8, self.base_int8
-            lo.train_mode, self.base8, self.base_int8 = False, False, False
+            train, lo.train_mode = lo.train_mode, False
             try:
-                return self._generate(input_ids, live_lora=True, **kw)
+                with self._decoding_on(weights):
+                    return self._generate(input_ids, live_lora=True, **kw)
             finally:
-                lo.train_mode, self.base8, self.base_int8 = saved
+                lo.train_mode = train
         if weights == "4bit":
             raise ValueError('weights="4bit" with un-merged LoRA adapters: generate() then runs on merged 16-bit COPIES, which have no 4-bit form - '
                              'call merge_lora() first (it re-quantises the merged weights, as peft does for a merged Linear4bit), or pass '
@@ -947,12 +863,8 @@ class TextModal:
             raise ValueError('weights="int8" with un-merged LoRA adapters: generate() then runs on merged 16-bit COPIES, which have no int8 form - '
                              'call merge_lora() first (it re-quantises the merged weights), or pass adapters="live" (the adapters then run '
                              'next to the int8 rows)')
-        base_layers, base8, base_i8 = self.p["layers"], self.base8, self.base_int8
-        self.p["layers"], self.base8, self.base_int8 = self._lora_merged_layers(), False, False   # merged 16-bit copies: no 8-bit operands of them exist
-        try:
+        with self._decoding_on(weights, self._lora_merged_layers()):   # merged 16-bit copies: no 8-bit operands of them exist
             return self._generate(input_ids, **kw)
-        finally:
-            self.p["layers"], self.base8, self.base_int8 = base_layers, base8, base_i8
 
     # ------------------------------------------------------------------ backward (activation gradients only)
     def backward(self, loss_scale: float = 1.0, need_input_grad: bool = True, on_layer_ready=None):
@@ -962,7 +874,7 @@ class TextModal:
         assert c is not None, "decode(save_ctx=True) must precede backward"
         B, S, desc, LT = c["B"], c["S"], c["desc"], c["LT"]
         d, H, hd, ff, p = self.d, self.heads, self.hd, self.ff, self.p
-        lo = self.lora
+        base, has = self.base, self._has  # the norm backwards and SwiGLU' hand the 8-bit operand of the next dX product on (None in bf16)
         M = B * S
         dhv = hk.gemm_nt(c["dlogits"], p["lm_headT"], alpha=loss_scale)
         tail = c.get("tail")
@@ -971,11 +883,7 @@ class TextModal:
             hk.scatter_rows(dhv, c["rows"], dhid)
         else:
             dhid = dhv  # x_last holds exactly the supervised rows: the last layer's backward starts compact
-        dxq = None
-        if self.base8:
-            dx, dxq = hk.rmsnorm_bwd_q(dhid, c["x_last"], p["norm_w"], None, eps=self.eps)
-        else:
-            dx = hk.rmsnorm_bwd(dhid, c["x_last"], p["norm_w"], None, eps=self.eps)
+        dx, dxq = base.norm_bwd(dhid, c["x_last"], p["norm_w"], self.eps)
         scale = 1.0 / math.sqrt(hd)
         delta = torch.empty((B, H, LT), device=self.device, dtype=torch.float32)
         dqkv = torch.empty((M, 3 * d), device=self.device, dtype=torch.bfloat16)
@@ -990,19 +898,12 @@ class TextModal:
                     on_layer_ready(li)
                 continue
             gu, qkv = s["gu"], s["qkv"]
-            dmq = None
-            act = hk.swiglu_fwd(gu, ff) if lo is not None and "down" in lo.groups else None      # x of the down projection
-            dgu = self._down_bwd(li, dx, L["down_wT"], gu, act, s.get("T_down"), q8=self._q8(L, "down_wT"), dyq=dxq, drop=self._drop(s, "down"))
-            dguq = None
-            if self.base8:
-                dgu, dguq = dgu
-            h2 = hk.rmsnorm_fwd(s["x_mid"], L["ln2_w"], self.eps) if lo is not None and "gu" in lo.groups else None
-            dh = self._lin_bwd(li, "gu", dgu, L["gu_wT"], h2, s.get("T_gu"), q8=self._q8(L, "gu_wT"), dyq=dguq, drop=self._drop(s, "gu"))
-            if self.base8:
-                dx_mid, dmq = hk.rmsnorm_bwd_q(dh, s["x_mid"], L["ln2_w"], None, add=dx, eps=self.eps, out=dh)
-            else:
-                dx_mid = hk.rmsnorm_bwd(dh, s["x_mid"], L["ln2_w"], None, add=dx, eps=self.eps, out=dh)
-            do = self._lin_bwd(li, "o", dx_mid, L["o_wT"], s["o"], s.get("T_o"), q8=self._q8(L, "o_wT"), dyq=dmq, drop=self._drop(s, "o"))
+            act = hk.swiglu_fwd(gu, ff) if has("down") else None      # x of the down projection
+            dgu, dguq = self._down_bwd(li, dx, L, gu, act, s.get("T_down"), dyq=dxq, drop=self._drop(s, "down"))
+            h2 = hk.rmsnorm_fwd(s["x_mid"], L["ln2_w"], self.eps) if has("gu") else None
+            dh = self._lin_bwd(li, "gu", dgu, L, h2, s.get("T_gu"), dyq=dguq, drop=self._drop(s, "gu"))
+            dx_mid, dmq = base.norm_bwd(dh, s["x_mid"], L["ln2_w"], self.eps, add=dx, out=dh)
+            do = self._lin_bwd(li, "o", dx_mid, L, s["o"], s.get("T_o"), dyq=dmq, drop=self._drop(s, "o"))
             adesc, max_q = desc, S
             if tl is not None:
                 rows_t, adesc, max_q = tl
@@ -1012,12 +913,9 @@ class TextModal:
             # delta = rowsum(dO * O) inside the dQ kernel (one launch and one pass over O / dO less), inverse RoPE in the dq / dk stores
             hk.attn_bwd_o(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], do, s["o_full"], s["lse"], delta, dqkv[:, :d], dqkv[:, d:2 * d],
                           dqkv[:, 2 * d:], adesc, B, H, hd, max_q, S, LT, True, scale, rope=(self.cos, self.sin, S, 0))
-            h1 = hk.rmsnorm_fwd(s["x_in"], L["ln1_w"], self.eps) if lo is not None and "qkv" in lo.groups else None
-            dh1 = self._lin_bwd(li, "qkv", dqkv, L["qkv_wT"], h1, s.get("T_qkv"), q8=self._q8(L, "qkv_wT"), drop=self._drop(s, "qkv"))
-            if self.base8:
-                dx, dxq = hk.rmsnorm_bwd_q(dh1, s["x_in"], L["ln1_w"], None, add=dx_mid, eps=self.eps, out=dh1)
-            else:
-                dx = hk.rmsnorm_bwd(dh1, s["x_in"], L["ln1_w"], None, add=dx_mid, eps=self.eps, out=dh1)
+            h1 = hk.rmsnorm_fwd(s["x_in"], L["ln1_w"], self.eps) if has("qkv") else None
+            dh1 = self._lin_bwd(li, "qkv", dqkv, L, h1, s.get("T_qkv"), drop=self._drop(s, "qkv"))
+            dx, dxq = base.norm_bwd(dh1, s["x_in"], L["ln1_w"], self.eps, add=dx_mid, out=dh1)
             s.clear()
             if on_layer_ready is not None:
                 on_layer_ready(li)

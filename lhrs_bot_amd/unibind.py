@@ -94,7 +94,7 @@ class UniBind:
                                       "model.enable_lora(...) first; full LLaMA fine-tuning is not on the reference's path")
         self.rgb_pooler.requires_grad = bool(tune_rgb_pooler)
         self.train()
-        if self.bits in (4, 8) and not (self.text.base8 or self.text.base_int8 or getattr(self.text, "base4", None)) and self.text.p.get("layers"):
+        if self.bits in (4, 8) and not (self.text.base8 or self.text.base_int8 or self.text.base4) and self.text.p.get("layers"):
             # the YAML's `bits: 8`: LLM.int8 storage and arithmetic of the (now loaded) frozen decoder linears, as the reference runs stages 2/3;
             # LHRS_BASE8=e4m3 selects the faster MI355X-native 8-bit base instead (a deviation: no outlier decomposition).
             # `bits: 4`: bitsandbytes 4-bit storage with the YAML's quant_type / double_quant (text_modal.py:97-101)

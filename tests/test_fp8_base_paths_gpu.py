@@ -21,8 +21,8 @@ import torch
 
 from lhrs_bot_amd import _lib
 from lhrs_bot_amd import kernels as hk
-from lhrs_bot_amd.text import IGNORE_INDEX, IMAGE_TOKEN_INDEX, TextModal
 
+import decoder_trace_cases as dc
 import fp8_base_cases as fc
 import gemm_cases as gc
 import rowwise_cases as rc
@@ -414,23 +414,7 @@ class Walk:
 
 
 # ------------------------------------------------------------------------------------------------------------------------- the model
-def make_model(setting, seed=3):
-    m = TextModal(device=DEV, max_pos=128, **fc.MODEL)
-    m.init_random(seed=seed)
-    g = torch.Generator().manual_seed(100 + seed)
-    for w in (m.p["layers"][0]["ln1_w"], m.p["layers"][0]["ln2_w"], m.p["norm_w"]):      # init_random leaves all three at 1: tell them apart
-        w.copy_((1 + 0.1 * torch.randn(w.shape, generator=g)).to(BF))
-    m.quantize_base(8, "e4m3")
-    kw = fc.SETTINGS[setting]
-    if kw is not None:
-        lo = m.enable_lora(seed=5, **kw)
-        g = torch.Generator().manual_seed(11)
-        for proj in kw["targets"]:                                       # B starts at zero in peft: the adapter term must show per element
-            A, B = lo.get_adapter(0, proj)
-            lo.set_adapter(0, proj, A.clone(), torch.randn(B.shape, generator=g) * 0.05)
-        lo.refresh()
-        assert lo.train_mode
-    return m
+make_model = dc.make_model          # the e4m3 base by default; shared with test_decoder_trace_gpu.py
 
 
 @pytest.fixture(scope="module")
@@ -466,9 +450,9 @@ def _drive(m, rec_factory, cell, opt):
         save = {}
         rec = rec_factory()
         if cell == "gu_fwd":
-            out = m._gu_fwd(0, h, Lw["gu_w"], save, q8=m._q8(Lw, "gu_w"), xq=hq)
+            out = m._gu_fwd(0, h, Lw, save, xq=hq)
         else:
-            out = m._lin(0, g, h, Lw[g + "_w"], residual=residual, save=save, q8=m._q8(Lw, g + "_w"), xq=hq, rope=rope)
+            out = m._lin(0, g, h, Lw, residual=residual, save=save, xq=hq, rope=rope)
 
         def walk(w):
             if cell == "gu_fwd":
@@ -492,14 +476,14 @@ def _drive(m, rec_factory, cell, opt):
     x = (hk.swiglu_fwd(gu, ff) if g == "down" else rnd(33, M, fin)) if has(g) else None
     save = {}
     if has(g):                                                            # the forward of this group: T and the dropout seed the backward needs
-        m._lin(0, g, x, Lw[g + "_w"], save=save, q8=m._q8(Lw, g + "_w"))
+        m._lin(0, g, x, Lw, save=save)
     dyq = hk.quant_fp8_rows(dy) if (cell == "down_bwd" or opt["dyq"]) else None
     gu0 = None if gu is None else gu.clone()
     rec = rec_factory()
     if cell == "down_bwd":
-        out = m._down_bwd(0, dy, Lw["down_wT"], gu, x, save.get("T_down"), q8=m._q8(Lw, "down_wT"), dyq=dyq, drop=m._drop(save, "down"))
+        out = m._down_bwd(0, dy, Lw, gu, x, save.get("T_down"), dyq=dyq, drop=m._drop(save, "down"))
     else:
-        out = m._lin_bwd(0, g, dy, Lw[g + "_wT"], x, save.get("T_" + g), q8=m._q8(Lw, g + "_wT"), dyq=dyq, drop=m._drop(save, g))
+        out = m._lin_bwd(0, g, dy, Lw, x, save.get("T_" + g), dyq=dyq, drop=m._drop(save, g))
 
     def walk(w):
         if has(g):
@@ -543,18 +527,7 @@ def test_e4m3_linear_call_by_call(setting, cell, models, monkeypatch):
 
 # ------------------------------------------------------------------------------------------------------------------------- 3. one layer
 def _batch():
-    """two sequences of 36 tokens with one <image> placeholder each, 5 image rows: S = 40, M = 80"""
-    g = torch.Generator().manual_seed(17)
-    B, T, NI = 2, 36, 5
-    ids = torch.randint(3, fc.MODEL["vocab"], (B, T), generator=g)
-    ids[:, 3] = IMAGE_TOKEN_INDEX
-    mask = torch.ones(B, T, dtype=torch.int64)
-    mask[1, 26:] = 0                                                      # the second sequence is right-padded: 30 keys after the splice
-    labels = torch.full((B, T), IGNORE_INDEX, dtype=torch.int64)
-    labels[0, 21:36] = ids[0, 21:36]                                       # labels on a contiguous tail of each sequence
-    labels[1, 16:26] = ids[1, 16:26]
-    image = (torch.randn(B, NI, fc.MODEL["dim"], generator=g) * 0.05).to(BF).to(DEV)
-    return ids, image, mask, labels
+    return dc.batch(DEV)
 
 
 def walk_layer(calls, m, x_in, rows, S):
