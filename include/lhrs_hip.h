@@ -264,6 +264,16 @@ int lhrs_attn_bwd_o(const void* q, long ldq, const void* k, long ldk, const void
                     const void* o, long ldo, const float* lse, float* delta, void* dq, long ld_dq, void* dk, long ld_dk, void* dv,
                     long ld_dv, const int* desc, int nseq, int H, int D, int max_q, int max_kv, int LTq, int causal, float scale,
                     const float* cos_t, const float* sin_t, int pos_mod, int pos0, long rows, void* stream);
+/* The plan of one attention call without running it (csrc/attn_plan.h: the host-only planner every entry point above but lhrs_attn_delta and
+ * lhrs_seq_transpose runs through; pure, no device work): which kernels the call launches, in launch order.  entry: 0 lhrs_attn_fwd,
+ * 1 lhrs_attn_fwd_kmask, 2 lhrs_attn_bwd, 3 lhrs_attn_bwd_rope, 4 lhrs_attn_bwd_o.  has_rope: cos / sin tables are given (entry 3 always, entry
+ * 4 when cos_t != NULL; the others take none).  out_wide: every output row stride is a multiple of 8 elements and every output pointer of 16
+ * bytes.  out_kernels: cap launches, each an index of lhrs_attn_kernel_name() - delta, fwd_res, fwd_tiled, dq_res, dq_tiled, dkv_res, dkv_tiled,
+ * rope_dq, rope_dk (the last two: lhrs_rope(inverse) over the dq / dk rows).  *out_flags: bit 0 the resident kernels store 16-byte rows, bit 1 the
+ * inverse RoPE rides in the resident kernels' stores, bit 2 the resident dQ kernel writes delta.  Returns the number of launches, -1 when
+ * rejected (head_dim, entry, entry 3 without tables, cap too small). */
+int lhrs_attn_plan(int entry, int D, int max_q, int max_kv, int LTq, int has_rope, int out_wide, int* out_kernels, int cap, int* out_flags);
+const char* lhrs_attn_kernel_name(int kernel);
 
 /* ---- element-wise / layout -------------------------------------------------------------------------- *
  * patchify/assemble: HF CLIPVisionEmbeddings (rgb_vision_modal.py:166-172); rope: HF apply_rotary_pos_emb;

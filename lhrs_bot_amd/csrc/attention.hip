@@ -27,7 +27,12 @@
 // group and instruction, which is exactly one half of an MFMA operand in the k-slot permutation above.
 // No transposed copies exist in HBM.  K/V (or Q/dO) tiles are prefetched global->registers while the previous tile is
 // multiplied, then written to LDS behind one barrier (latency hidden behind the MFMAs).
+//
+// Dispatch.  Which of the tiled and the LDS-resident kernels a call launches, in which order, and where the inverse RoPE and delta happen is decided
+// by the host-only planner attn_plan.h (exported as lhrs_attn_plan); the entry points at the end of this file validate, fill AttnArgs and walk the plan.
 #include "common.h"
+#include "attn_plan.h"
+#include "../../include/lhrs_hip.h"
 #include <type_traits>
 
 namespace {
@@ -216,6 +221,32 @@ __device__ __forceinline__ void rope_bwd_inplace(f32x4 (&g)[DB], const AttnArgs&
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
 
+// ---- steps the kernels share ----------------------------------------------------------------------------------------------------------------
+// A helper is used only where the kernel's machine code stays byte for byte what the written-out lines give; elsewhere the lines stay written out.
+// Measured per kernel against the build without the helper (the compiler simplifies a helper on its own before inlining it, which can reorder the
+// kernel's IR and with it the schedule):
+//   read_desc       all six kernels
+//   load_row_frags  the two forward kernels; the q | dO and k | v pairs (one call each, or one interleaved call) move both dQ kernels and the tiled dK/dV kernel
+//   zero            all but attn_bwd_dq_res_kernel
+// Tried and left written out because they moved instructions: the score products (every kernel), the transposed accumulation (both forward and both dQ
+// kernels), the TrAddr rebase and the wide-or-narrow row store (all three resident kernels), the K/V staging (resident forward and dQ).
+struct SeqDesc { int q_off, q_len, kv_off, kv_len, kv_rows, coff; };  // one 8-int record of a.desc
+__device__ __forceinline__ SeqDesc read_desc(const int* desc, int seq) {
+  const int* ds = desc + seq * 8;
+  return SeqDesc{ds[0], ds[1], ds[2], ds[3], ds[4], ds[5]};
+}
+// the KS = D / 32 MFMA B-operand fragments of one token row (`row` points at dim 0 of the head): lane group fg holds dims ks * 32 + fg * 8 + 0..7
+template <int KS>
+__device__ __forceinline__ void load_row_frags(bf16x8 (&f)[KS], const bf16_t* row, int fg) {
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) f[ks] = *reinterpret_cast<const bf16x8*>(row + ks * 32 + fg * 8);
+}
+template <int N>
+__device__ __forceinline__ void zero(f32x4 (&v)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 // ---------------------------------------------------------------- forward
 template <int D, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
@@ -223,32 +254,29 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char lds_k[64 * D * 2];
   __shared__ __attribute__((aligned(16))) char lds_v[64 * D * 2];
   const int seq = blockIdx.z, h = blockIdx.y;
-  const int* ds = a.desc + seq * 8;
-  const int q_off = ds[0], q_len = ds[1], kv_off = ds[2], kv_len = ds[3], coff = ds[5];
+  const SeqDesc sd = read_desc(a.desc, seq);
   const int q0 = blockIdx.x * 64;
-  if (q0 >= q_len) return;
+  if (q0 >= sd.q_len) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
   const int qrow = q0 + wave * 16 + fr;
-  const bf16_t* qp = a.q + (long)(q_off + min(qrow, q_len - 1)) * a.ldq + h * D;
+  const bf16_t* qp = a.q + (long)(sd.q_off + min(qrow, sd.q_len - 1)) * a.ldq + h * D;
   bf16x8 qf[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 32 + fg * 8);
+  load_row_frags<KS>(qf, qp, fg);
 
   float m = NEG_INF, l = 0.f;
   f32x4 o[DB];
-#pragma unroll
-  for (int i = 0; i < DB; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero<DB>(o);
 
   const unsigned char* km = a.kmask ? a.kmask + (long)seq * a.ld_kmask : nullptr;
-  int kv_end = kv_len;
-  if (CAUSAL) kv_end = max(0, min(kv_len, q0 + 64 + coff));
+  int kv_end = sd.kv_len;
+  if (CAUSAL) kv_end = max(0, min(sd.kv_len, q0 + 64 + sd.coff));
   const int ntiles = (kv_end + 63) >> 6;
-  const bf16_t* kbase = a.k + (long)kv_off * a.ldk + h * D;
-  const bf16_t* vbase = a.v + (long)kv_off * a.ldv + h * D;
+  const bf16_t* kbase = a.k + (long)sd.kv_off * a.ldk + h * D;
+  const bf16_t* vbase = a.v + (long)sd.kv_off * a.ldv + h * D;
   TrAddr<D> tv;
   tv.init(lds_v, lane);
   TileRegs<D> kr, vr;
-  if (ntiles > 0) { tile_load<D>(kr, kbase, a.ldk, 0, kv_len, tid); tile_load<D>(vr, vbase, a.ldv, 0, kv_len, tid); }
+  if (ntiles > 0) { tile_load<D>(kr, kbase, a.ldk, 0, sd.kv_len, tid); tile_load<D>(vr, vbase, a.ldv, 0, sd.kv_len, tid); }
 
   for (int j = 0; j < ntiles; ++j) {
     __syncthreads();  // every wave is done reading tile j-1
@@ -256,8 +284,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
     tile_store<D>(lds_v, vr, tid);
     __syncthreads();
     if (j + 1 < ntiles) {  // prefetch tile j+1 into registers; the loads fly while tile j is multiplied
-      tile_load<D>(kr, kbase, a.ldk, (j + 1) * 64, kv_len, tid);
-      tile_load<D>(vr, vbase, a.ldv, (j + 1) * 64, kv_len, tid);
+      tile_load<D>(kr, kbase, a.ldk, (j + 1) * 64, sd.kv_len, tid);
+      tile_load<D>(vr, vbase, a.ldv, (j + 1) * 64, sd.kv_len, tid);
     }
     f32x4 s[4];
 #pragma unroll
@@ -274,7 +302,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = j * 64 + nb * 16 + fg * 4 + r;
-        bool ok = key < kv_len && (!CAUSAL || key <= qrow + coff);
+        bool ok = key < sd.kv_len && (!CAUSAL || key <= qrow + sd.coff);
         if (km != nullptr && ok) ok = km[key] != 0;
         s[nb][r] = ok ? s[nb][r] * a.scale : NEG_INF;
         mx = fmaxf(mx, s[nb][r]);
@@ -306,9 +334,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
     for (int db = 0; db < DB; ++db) o[db] = MFMA(join(v1lo[db], v1hi[db]), p1, o[db]);
   }
-  if (qrow < q_len) {
+  if (qrow < sd.q_len) {
     const float inv = l > 0.f ? 1.f / l : 0.f;
-    bf16_t* op = a.o + (long)(q_off + qrow) * a.ldo + h * D + fg * 4;
+    bf16_t* op = a.o + (long)(sd.q_off + qrow) * a.ldo + h * D + fg * 4;
 #pragma unroll
     for (int db = 0; db < DB; ++db) store4bf(op + db * 16, o[db], inv);
     if (a.lse && fg == 0) a.lse[(long)(seq * a.H + h) * a.LTq + qrow] = (l > 0.f) ? m + __logf(l) : NEG_INF;
@@ -322,15 +350,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char lds_k[64 * D * 2];
   __shared__ __attribute__((aligned(16))) char lds_v[64 * D * 2];
   const int seq = blockIdx.z, h = blockIdx.y;
-  const int* ds = a.desc + seq * 8;
-  const int q_off = ds[0], q_len = ds[1], kv_off = ds[2], kv_len = ds[3], coff = ds[5];
+  const SeqDesc sd = read_desc(a.desc, seq);
   const int q0 = blockIdx.x * 64;
-  if (q0 >= q_len) return;
+  if (q0 >= sd.q_len) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
   const int qrow = q0 + wave * 16 + fr;
-  const int qrow_c = min(qrow, q_len - 1);
-  const bf16_t* qp = a.q + (long)(q_off + qrow_c) * a.ldq + h * D;
-  const bf16_t* dop = a.dout + (long)(q_off + qrow_c) * a.ld_do + h * D;
+  const int qrow_c = min(qrow, sd.q_len - 1);
+  const bf16_t* qp = a.q + (long)(sd.q_off + qrow_c) * a.ldq + h * D;
+  const bf16_t* dop = a.dout + (long)(sd.q_off + qrow_c) * a.ld_do + h * D;
   bf16x8 qf[KS], dof[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
@@ -340,18 +367,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
   const long stat = (long)(seq * a.H + h) * a.LTq + qrow_c;
   const float lse_q = a.lse[stat], delta_q = a.delta[stat];
   f32x4 dq[DB];
-#pragma unroll
-  for (int i = 0; i < DB; ++i) dq[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero<DB>(dq);
 
-  int kv_end = kv_len;
-  if (CAUSAL) kv_end = max(0, min(kv_len, q0 + 64 + coff));
+  int kv_end = sd.kv_len;
+  if (CAUSAL) kv_end = max(0, min(sd.kv_len, q0 + 64 + sd.coff));
   const int ntiles = (kv_end + 63) >> 6;
-  const bf16_t* kbase = a.k + (long)kv_off * a.ldk + h * D;
-  const bf16_t* vbase = a.v + (long)kv_off * a.ldv + h * D;
+  const bf16_t* kbase = a.k + (long)sd.kv_off * a.ldk + h * D;
+  const bf16_t* vbase = a.v + (long)sd.kv_off * a.ldv + h * D;
   TrAddr<D> tk;
   tk.init(lds_k, lane);
   TileRegs<D> kr, vr;
-  if (ntiles > 0) { tile_load<D>(kr, kbase, a.ldk, 0, kv_len, tid); tile_load<D>(vr, vbase, a.ldv, 0, kv_len, tid); }
+  if (ntiles > 0) { tile_load<D>(kr, kbase, a.ldk, 0, sd.kv_len, tid); tile_load<D>(vr, vbase, a.ldv, 0, sd.kv_len, tid); }
 
   for (int j = 0; j < ntiles; ++j) {
     __syncthreads();
@@ -359,8 +385,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
     tile_store<D>(lds_v, vr, tid);
     __syncthreads();
     if (j + 1 < ntiles) {
-      tile_load<D>(kr, kbase, a.ldk, (j + 1) * 64, kv_len, tid);
-      tile_load<D>(vr, vbase, a.ldv, (j + 1) * 64, kv_len, tid);
+      tile_load<D>(kr, kbase, a.ldk, (j + 1) * 64, sd.kv_len, tid);
+      tile_load<D>(vr, vbase, a.ldv, (j + 1) * 64, sd.kv_len, tid);
     }
     f32x4 s[4], dp[4];
 #pragma unroll
@@ -380,7 +406,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = j * 64 + nb * 16 + fg * 4 + r;
-        const bool ok = key < kv_len && (!CAUSAL || key <= qrow + coff) && qrow < q_len;
+        const bool ok = key < sd.kv_len && (!CAUSAL || key <= qrow + sd.coff) && qrow < sd.q_len;
         const float p = ok ? __expf(s[nb][r] * a.scale - lse_q) : 0.f;
         s[nb][r] = ok ? p * (dp[nb][r] - delta_q) * a.scale : 0.f;  // dS
       }
@@ -394,8 +420,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
 #pragma unroll
     for (int db = 0; db < DB; ++db) dq[db] = MFMA(join(k1lo[db], k1hi[db]), d1, dq[db]);
   }
-  if (qrow < q_len) {
-    bf16_t* p = a.dq + (long)(q_off + qrow) * a.ld_dq + h * D + fg * 4;
+  if (qrow < sd.q_len) {
+    bf16_t* p = a.dq + (long)(sd.q_off + qrow) * a.ld_dq + h * D + fg * 4;
 #pragma unroll
     for (int db = 0; db < DB; ++db) store4bf(p + db * 16, dq[db], 1.f);
   }
@@ -410,15 +436,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) float lds_lse[64];
   __shared__ __attribute__((aligned(16))) float lds_delta[64];
   const int seq = blockIdx.z, h = blockIdx.y;
-  const int* ds = a.desc + seq * 8;
-  const int q_off = ds[0], q_len = ds[1], kv_off = ds[2], kv_len = ds[3], kv_rows = ds[4], coff = ds[5];
+  const SeqDesc sd = read_desc(a.desc, seq);
   const int k0 = blockIdx.x * 64;
-  if (k0 >= kv_rows) return;
+  if (k0 >= sd.kv_rows) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
   const int key = k0 + wave * 16 + fr;
-  const int key_c = min(key, kv_rows - 1);
-  const bf16_t* kp = a.k + (long)(kv_off + key_c) * a.ldk + h * D;
-  const bf16_t* vp = a.v + (long)(kv_off + key_c) * a.ldv + h * D;
+  const int key_c = min(key, sd.kv_rows - 1);
+  const bf16_t* kp = a.k + (long)(sd.kv_off + key_c) * a.ldk + h * D;
+  const bf16_t* vp = a.v + (long)(sd.kv_off + key_c) * a.ldv + h * D;
   bf16x8 kf[KS], vf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
@@ -426,14 +451,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
     vf[ks] = *reinterpret_cast<const bf16x8*>(vp + ks * 32 + fg * 8);
   }
   f32x4 dk[DB], dv[DB];
-#pragma unroll
-  for (int i = 0; i < DB; ++i) { dk[i] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  zero<DB>(dk);
+  zero<DB>(dv);
 
-  const int nq_tiles = (q_len + 63) >> 6;
+  const int nq_tiles = (sd.q_len + 63) >> 6;
   int i0 = 0;
-  if (CAUSAL) i0 = max(0, (k0 - coff) >> 6);  // first q tile that can see key k0 (q >= key - coff)
-  const bf16_t* qbase = a.q + (long)q_off * a.ldq + h * D;
-  const bf16_t* dobase = a.dout + (long)q_off * a.ld_do + h * D;
+  if (CAUSAL) i0 = max(0, (k0 - sd.coff) >> 6);  // first q tile that can see key k0 (q >= key - coff)
+  const bf16_t* qbase = a.q + (long)sd.q_off * a.ldq + h * D;
+  const bf16_t* dobase = a.dout + (long)sd.q_off * a.ld_do + h * D;
   const float* lsebase = a.lse + (long)(seq * a.H + h) * a.LTq;
   const float* deltabase = a.delta + (long)(seq * a.H + h) * a.LTq;
   TrAddr<D> tq, tdo;
@@ -442,8 +467,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
   TileRegs<D> qr, dor;
   float stat_r = 0.f;
   auto prefetch = [&](int i) {
-    tile_load<D>(qr, qbase, a.ldq, i * 64, q_len, tid);
-    tile_load<D>(dor, dobase, a.ld_do, i * 64, q_len, tid);
+    tile_load<D>(qr, qbase, a.ldq, i * 64, sd.q_len, tid);
+    tile_load<D>(dor, dobase, a.ld_do, i * 64, sd.q_len, tid);
     if (tid < 64) stat_r = lsebase[i * 64 + tid];
     else if (tid < 128) stat_r = deltabase[i * 64 + tid - 64];
   };
@@ -477,7 +502,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int q = i * 64 + qb * 16 + fg * 4 + r;
-        const bool ok = q < q_len && key < kv_len && (!CAUSAL || key <= q + coff);
+        const bool ok = q < sd.q_len && key < sd.kv_len && (!CAUSAL || key <= q + sd.coff);
         const float p = ok ? __expf(s[qb][r] * a.scale - lq[r]) : 0.f;
         dp[qb][r] = ok ? p * (dp[qb][r] - dl[r]) * a.scale : 0.f;  // dS
         s[qb][r] = p;                                               // P
@@ -504,9 +529,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
 #pragma unroll
     for (int db = 0; db < DB; ++db) dk[db] = MFMA(join(blo[db], bhi[db]), d1, dk[db]);
   }
-  if (key < kv_rows) {
-    bf16_t* pk = a.dk + (long)(kv_off + key) * a.ld_dk + h * D + fg * 4;
-    bf16_t* pv = a.dv + (long)(kv_off + key) * a.ld_dv + h * D + fg * 4;
+  if (key < sd.kv_rows) {
+    bf16_t* pk = a.dk + (long)(sd.kv_off + key) * a.ld_dk + h * D + fg * 4;
+    bf16_t* pv = a.dv + (long)(sd.kv_off + key) * a.ld_dv + h * D + fg * 4;
 #pragma unroll
     for (int db = 0; db < DB; ++db) { store4bf(pk + db * 16, dk[db], 1.f); store4bf(pv + db * 16, dv[db], 1.f); }
   }
@@ -520,7 +545,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
 // each wave walks 16-row groups on its own - no further barriers, no per-tile global loads.  Groups are dealt to waves
 // in a zig-zag over descending causal cost so that every wave gets (almost) the same number of 64-key tiles.
 // ================================================================================================
-template <int D> constexpr int res_rows() { return 163840 / (2 * D * 2); }
+using attn_plan_h::attn_res_rows;  // rows of one operand matrix in the resident image
 
 // DMA `rows` (multiple of 64, <= res_rows) rows of a [*, D] bf16 matrix into the swizzled resident image
 template <int D>
@@ -565,20 +590,19 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_res_kernel(AttnArgs a) {
   constexpr int KS = D / 32, DB = D / 16, TILE = 64 * D * 2;
   __shared__ __attribute__((aligned(16))) char smem[163840];
   char* lds_k = smem;
-  char* lds_v = smem + res_rows<D>() * D * 2;
+  char* lds_v = smem + attn_res_rows(D) * D * 2;
   const int seq = blockIdx.y, h = blockIdx.x;
-  const int* ds = a.desc + seq * 8;
-  const int q_off = ds[0], q_len = ds[1], kv_off = ds[2], kv_len = ds[3], coff = ds[5];
+  const SeqDesc sd = read_desc(a.desc, seq);
   const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fg = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   DIAG_DECL(0);
   DIAG_T(0);
-  int kv_need = kv_len;
-  if (CAUSAL) kv_need = max(0, min(kv_len, q_len + coff));
+  int kv_need = sd.kv_len;
+  if (CAUSAL) kv_need = max(0, min(sd.kv_len, sd.q_len + sd.coff));
   const int rows = ((kv_need + 63) >> 6) << 6;
   if (rows > 0) {
-    res_load<D>(lds_k, a.k + (long)kv_off * a.ldk + h * D, a.ldk, rows, kv_len, lane, wave);
-    res_load<D>(lds_v, a.v + (long)kv_off * a.ldv + h * D, a.ldv, rows, kv_len, lane, wave);
+    res_load<D>(lds_k, a.k + (long)sd.kv_off * a.ldk + h * D, a.ldk, rows, sd.kv_len, lane, wave);
+    res_load<D>(lds_v, a.v + (long)sd.kv_off * a.ldv + h * D, a.ldv, rows, sd.kv_len, lane, wave);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -586,25 +610,23 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_res_kernel(AttnArgs a) {
   TrAddr<D> tv;
   tv.init(lds_v, lane);
   const float c2 = a.scale * 1.4426950408889634f;  // scale * log2(e)
-  const int G = (q_len + 15) >> 4;
+  const int G = (sd.q_len + 15) >> 4;
   for (int p = 0;; ++p) {
     const int g = zigzag_group(p, wave, G, CAUSAL);
     if (g < 0) break;
     DIAG_MARK();
     const int qrow = g * 16 + fr;
-    const bf16_t* qp = a.q + (long)(q_off + min(qrow, q_len - 1)) * a.ldq + h * D;
+    const bf16_t* qp = a.q + (long)(sd.q_off + min(qrow, sd.q_len - 1)) * a.ldq + h * D;
     bf16x8 qf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 32 + fg * 8);
+    load_row_frags<KS>(qf, qp, fg);
     DIAG_ACC(0);
     float m = NEG_INF, l = 0.f;
     f32x4 o[DB];
-#pragma unroll
-    for (int i = 0; i < DB; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    int kv_end = kv_len;
+    zero<DB>(o);
+    int kv_end = sd.kv_len;
     // the last key any STORED row of the group sees: a partial last group (rows past q_len) must not reach past the kv_need rows loaded above -
     // with causal_off > 0 that can be another 64-key tile, whose LDS rows hold whatever the previous workgroup left there (NaN * 0 = NaN)
-    if (CAUSAL) kv_end = max(0, min(kv_len, min(g * 16 + 16, q_len) + coff));
+    if (CAUSAL) kv_end = max(0, min(sd.kv_len, min(g * 16 + 16, sd.q_len) + sd.coff));
     const int ntiles = (kv_end + 63) >> 6;
     for (int j = 0; j < ntiles; ++j) {
       const char* kt = lds_k + j * TILE;
@@ -623,14 +645,14 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_res_kernel(AttnArgs a) {
       // The kernel is VALU-bound (the softmax of a 64-key tile was ~200 VALU instructions against 32 MFMAs), so: (1) only a tile that
       // crosses the causal diagonal or the end of the keys computes the mask - a wave-uniform test; (2) the running maximum m is kept in
       // RAW score units and exp(scale * s - scale * m) is ONE fma into v_exp_f32 (exp2) with c2 = scale * log2(e)
-      const bool full = (j + 1) * 64 <= kv_len && (!CAUSAL || j * 64 + 63 <= g * 16 + coff);
+      const bool full = (j + 1) * 64 <= sd.kv_len && (!CAUSAL || j * 64 + 63 <= g * 16 + sd.coff);
       if (!full) {
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = j * 64 + nb * 16 + fg * 4 + r;
-            const bool ok = key < kv_len && (!CAUSAL || key <= qrow + coff);
+            const bool ok = key < sd.kv_len && (!CAUSAL || key <= qrow + sd.coff);
             s[nb][r] = ok ? s[nb][r] : NEG_INF;
           }
       }
@@ -669,9 +691,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_res_kernel(AttnArgs a) {
     DIAG_ACC(1);
     DIAG_UNITS(ntiles);
     l = group_sum(l);
-    if (qrow < q_len) {
+    if (qrow < sd.q_len) {
       const float inv = l > 0.f ? 1.f / l : 0.f;
-      bf16_t* op = a.o + (long)(q_off + qrow) * a.ldo + h * D;
+      bf16_t* op = a.o + (long)(sd.q_off + qrow) * a.ldo + h * D;
       if (a.wide) store_row_wide<DB>(op, o, inv, fg);
       else {
 #pragma unroll
@@ -690,35 +712,34 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_res_kernel(AttnArgs a) {
   constexpr int KS = D / 32, DB = D / 16, TILE = 64 * D * 2;
   __shared__ __attribute__((aligned(16))) char smem[163840];
   char* lds_k = smem;
-  char* lds_v = smem + res_rows<D>() * D * 2;
+  char* lds_v = smem + attn_res_rows(D) * D * 2;
   const int seq = blockIdx.y, h = blockIdx.x;
-  const int* ds = a.desc + seq * 8;
-  const int q_off = ds[0], q_len = ds[1], kv_off = ds[2], kv_len = ds[3], coff = ds[5];
+  const SeqDesc sd = read_desc(a.desc, seq);
   const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fg = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   DIAG_DECL(1);
   DIAG_T(0);
-  int kv_need = kv_len;
-  if (CAUSAL) kv_need = max(0, min(kv_len, q_len + coff));
+  int kv_need = sd.kv_len;
+  if (CAUSAL) kv_need = max(0, min(sd.kv_len, sd.q_len + sd.coff));
   const int rows = ((kv_need + 63) >> 6) << 6;
   if (rows > 0) {
-    res_load<D>(lds_k, a.k + (long)kv_off * a.ldk + h * D, a.ldk, rows, kv_len, lane, wave);
-    res_load<D>(lds_v, a.v + (long)kv_off * a.ldv + h * D, a.ldv, rows, kv_len, lane, wave);
+    res_load<D>(lds_k, a.k + (long)sd.kv_off * a.ldk + h * D, a.ldk, rows, sd.kv_len, lane, wave);
+    res_load<D>(lds_v, a.v + (long)sd.kv_off * a.ldv + h * D, a.ldv, rows, sd.kv_len, lane, wave);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   DIAG_T(1);
   TrAddr<D> tk;
   tk.init(lds_k, lane);
-  const int G = (q_len + 15) >> 4;
+  const int G = (sd.q_len + 15) >> 4;
   for (int p = 0;; ++p) {
     const int g = zigzag_group(p, wave, G, CAUSAL);
     if (g < 0) break;
     DIAG_MARK();
     const int qrow = g * 16 + fr;
-    const int qrow_c = min(qrow, q_len - 1);
-    const bf16_t* qp = a.q + (long)(q_off + qrow_c) * a.ldq + h * D;
-    const bf16_t* dop = a.dout + (long)(q_off + qrow_c) * a.ld_do + h * D;
+    const int qrow_c = min(qrow, sd.q_len - 1);
+    const bf16_t* qp = a.q + (long)(sd.q_off + qrow_c) * a.ldq + h * D;
+    const bf16_t* dop = a.dout + (long)(sd.q_off + qrow_c) * a.ld_do + h * D;
     bf16x8 qf[KS], dof[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -728,7 +749,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_res_kernel(AttnArgs a) {
     const long stat = (long)(seq * a.H + h) * a.LTq + qrow_c;
     float delta_q;
     if (a.o_in != nullptr) {  // delta of this row from the dO fragments already in registers and the matching O fragments
-      const bf16_t* op = a.o_in + (long)(q_off + qrow_c) * a.ld_oin + h * D;
+      const bf16_t* op = a.o_in + (long)(sd.q_off + qrow_c) * a.ld_oin + h * D;
       float part = 0.f;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
@@ -737,7 +758,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_res_kernel(AttnArgs a) {
         for (int e = 0; e < 8; ++e) part += bf2f((bf16_t)dof[ks][e]) * bf2f((bf16_t)of[e]);
       }
       delta_q = group_sum(part);
-      if (fg == 0 && qrow < q_len) a.delta_w[stat] = delta_q;
+      if (fg == 0 && qrow < sd.q_len) a.delta_w[stat] = delta_q;
     } else {
       delta_q = a.delta[stat];
     }
@@ -746,8 +767,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_res_kernel(AttnArgs a) {
     f32x4 dq[DB];
 #pragma unroll
     for (int i = 0; i < DB; ++i) dq[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    int kv_end = kv_len;
-    if (CAUSAL) kv_end = max(0, min(kv_len, min(g * 16 + 16, q_len) + coff));  // within the kv_need rows loaded (forward kernel)
+    int kv_end = sd.kv_len;
+    if (CAUSAL) kv_end = max(0, min(sd.kv_len, min(g * 16 + 16, sd.q_len) + sd.coff));  // within the kv_need rows loaded (forward kernel)
     const int ntiles = (kv_end + 63) >> 6;
     for (int j = 0; j < ntiles; ++j) {
       const char* kt = lds_k + j * TILE;
@@ -771,7 +792,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_res_kernel(AttnArgs a) {
       // VALU diet (see the forward kernel): P = exp2(s * c2 - lse * log2 e) is one fma + v_exp_f32, dS / scale = P * (dP - delta) (the
       // scale goes on the finished dQ rows), and only a tile on the causal diagonal / past the last key computes the mask.  Rows beyond q_len compute
       // garbage in their own lanes and are not stored.
-      const bool full = (j + 1) * 64 <= kv_len && (!CAUSAL || j * 64 + 63 <= g * 16 + coff);
+      const bool full = (j + 1) * 64 <= sd.kv_len && (!CAUSAL || j * 64 + 63 <= g * 16 + sd.coff);
       if (full) {
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb)
@@ -786,7 +807,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_res_kernel(AttnArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = j * 64 + nb * 16 + fg * 4 + r;
-            const bool ok = key < kv_len && (!CAUSAL || key <= qrow + coff) && qrow < q_len;
+            const bool ok = key < sd.kv_len && (!CAUSAL || key <= qrow + sd.coff) && qrow < sd.q_len;
             const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[nb][r], c2, -lse2));
             s[nb][r] = ok ? pv * (dp[nb][r] - delta_q) : 0.f;
           }
@@ -803,11 +824,11 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_res_kernel(AttnArgs a) {
     }
     DIAG_ACC(1);
     DIAG_UNITS(ntiles);
-    if (qrow < q_len) {
+    if (qrow < sd.q_len) {
 #pragma unroll
       for (int db = 0; db < DB; ++db) dq[db] *= a.scale;
-      if (a.rope_cos != nullptr) rope_bwd_inplace<DB>(dq, a, (long)q_off + qrow, fg);
-      bf16_t* pq = a.dq + (long)(q_off + qrow) * a.ld_dq + h * D;
+      if (a.rope_cos != nullptr) rope_bwd_inplace<DB>(dq, a, (long)sd.q_off + qrow, fg);
+      bf16_t* pq = a.dq + (long)(sd.q_off + qrow) * a.ld_dq + h * D;
       if (a.wide) store_row_wide<DB>(pq, dq, 1.f, fg);
       else {
 #pragma unroll
@@ -825,28 +846,27 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_res_kernel(AttnArgs a) {
   constexpr int KS = D / 32, DB = D / 16, TILE = 64 * D * 2;
   __shared__ __attribute__((aligned(16))) char smem[163840];
   char* lds_q = smem;
-  char* lds_do = smem + res_rows<D>() * D * 2;
+  char* lds_do = smem + attn_res_rows(D) * D * 2;
   const int seq = blockIdx.y, h = blockIdx.x;
-  const int* ds = a.desc + seq * 8;
-  const int q_off = ds[0], q_len = ds[1], kv_off = ds[2], kv_len = ds[3], kv_rows = ds[4], coff = ds[5];
+  const SeqDesc sd = read_desc(a.desc, seq);
   const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fg = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   DIAG_DECL(2);
   DIAG_T(0);
-  const int nq_tiles = (q_len + 63) >> 6;
+  const int nq_tiles = (sd.q_len + 63) >> 6;
   // Round 6.  (1) A last query tile with at most 32 rows (S = 273: 17) is a HALF tile: its rows 32..63 are neither loaded nor multiplied (their P and dS are zero:
   // skipping the products changes no bit).  (2) The space that frees behind the Q image holds the row statistics lse | delta of the whole sequence (2 x LTq floats):
   // round 5 read them from L2 / HBM in front of every tile - a dependent global round trip of 1-2 us per tile on a loaded chip, 2.8 us per tile against the forward
   // kernel's 0.9 (tools/attn_diag.py) - now they are LDS reads behind the same barrier as the operands, read where they are used.  The host sends a sequence whose
-  // image leaves no room for them (more than 288 queries at head_dim 128) to the tiled kernel (dkv_res_fits).
-  const bool half_last = nq_tiles > 0 && q_len - (nq_tiles - 1) * 64 <= 32;
+  // image leaves no room for them (more than 288 queries at head_dim 128) to the tiled kernel (attn_plan.h: dkv_res).
+  const bool half_last = nq_tiles > 0 && sd.q_len - (nq_tiles - 1) * 64 <= 32;
   const int rows_alloc = nq_tiles * 64 - (half_last ? 32 : 0);
   float* lds_lse = reinterpret_cast<float*>(smem + rows_alloc * D * 2);
   float* lds_delta = lds_lse + a.LTq;
   const float* lsebase = a.lse + (long)(seq * a.H + h) * a.LTq;
   const float* deltabase = a.delta + (long)(seq * a.H + h) * a.LTq;
-  res_load<D>(lds_q, a.q + (long)q_off * a.ldq + h * D, a.ldq, rows_alloc, q_len, lane, wave);
-  res_load<D>(lds_do, a.dout + (long)q_off * a.ld_do + h * D, a.ld_do, rows_alloc, q_len, lane, wave);
+  res_load<D>(lds_q, a.q + (long)sd.q_off * a.ldq + h * D, a.ldq, rows_alloc, sd.q_len, lane, wave);
+  res_load<D>(lds_do, a.dout + (long)sd.q_off * a.ld_do + h * D, a.ld_do, rows_alloc, sd.q_len, lane, wave);
   for (int t = tid; t < a.LTq; t += 512) { lds_lse[t] = lsebase[t]; lds_delta[t] = deltabase[t]; }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -854,15 +874,15 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_res_kernel(AttnArgs a) {
   TrAddr<D> tq, tdo;
   tq.init(lds_q, lane);
   tdo.init(lds_do, lane);
-  const int G = (kv_rows + 15) >> 4;
+  const int G = (sd.kv_rows + 15) >> 4;
   for (int p = 0;; ++p) {
     const int g = zigzag_group(p, wave, G, !CAUSAL);  // causal: low key groups see the most query tiles
     if (g < 0) break;
     DIAG_MARK();
     const int key = g * 16 + fr;
-    const int key_c = min(key, kv_rows - 1);
-    const bf16_t* kp = a.k + (long)(kv_off + key_c) * a.ldk + h * D;
-    const bf16_t* vp = a.v + (long)(kv_off + key_c) * a.ldv + h * D;
+    const int key_c = min(key, sd.kv_rows - 1);
+    const bf16_t* kp = a.k + (long)(sd.kv_off + key_c) * a.ldk + h * D;
+    const bf16_t* vp = a.v + (long)(sd.kv_off + key_c) * a.ldv + h * D;
     bf16x8 kf[KS], vf[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -870,10 +890,10 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_res_kernel(AttnArgs a) {
       vf[ks] = *reinterpret_cast<const bf16x8*>(vp + ks * 32 + fg * 8);
     }
     f32x4 dk[DB], dv[DB];
-#pragma unroll
-    for (int i = 0; i < DB; ++i) { dk[i] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    zero<DB>(dk);
+    zero<DB>(dv);
     int i0 = 0;
-    if (CAUSAL) i0 = max(0, (g * 16 - coff) >> 6);
+    if (CAUSAL) i0 = max(0, (g * 16 - sd.coff) >> 6);
     DIAG_ACC(0);
     DIAG_UNITS(nq_tiles - i0);
     for (int i = i0; i < nq_tiles; ++i) {
@@ -909,7 +929,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_res_kernel(AttnArgs a) {
       bf16x4 alo[DB], ahi[DB];
       // only a tile on the causal diagonal, past the last query or past the last key computes the mask (a wave-uniform test: this wave's keys
       // are g*16 .. g*16+15): the 16 index computations + compares + selects were a third of the loop's VALU work
-      const bool full = (i + 1) * 64 <= q_len && g * 16 + 15 < kv_len && (!CAUSAL || g * 16 + 15 <= i * 64 + coff);
+      const bool full = (i + 1) * 64 <= sd.q_len && g * 16 + 15 < sd.kv_len && (!CAUSAL || g * 16 + 15 <= i * 64 + sd.coff);
       auto probs = [&](const int qb) {  // s[qb] <- P, dp[qb] <- dS of query block qb; its row statistics come out of the LDS here
         const f32x4 lq = *reinterpret_cast<const f32x4*>(lds_lse + i * 64 + qb * 16 + fg * 4);
         const f32x4 dl = *reinterpret_cast<const f32x4*>(lds_delta + i * 64 + qb * 16 + fg * 4);
@@ -924,7 +944,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_res_kernel(AttnArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int q = i * 64 + qb * 16 + fg * 4 + r;
-            const bool ok = q < q_len && key < kv_len && (!CAUSAL || key <= q + coff);
+            const bool ok = q < sd.q_len && key < sd.kv_len && (!CAUSAL || key <= q + sd.coff);
             const float pv = ok ? __expf(s[qb][r] * a.scale - lq[r]) : 0.f;
             dp[qb][r] = ok ? pv * (dp[qb][r] - dl[r]) * a.scale : 0.f;
             s[qb][r] = pv;
@@ -962,12 +982,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_res_kernel(AttnArgs a) {
     }
     RopeRow<DB> rr;
     const bool rope = a.rope_cos != nullptr;
-    if (rope) rope_row_load<DB>(rr, a, (long)kv_off + key_c, fg);
+    if (rope) rope_row_load<DB>(rr, a, (long)sd.kv_off + key_c, fg);
     DIAG_ACC(1);
-    if (key < kv_rows) {
+    if (key < sd.kv_rows) {
       if (rope) rope_row_apply<DB>(dk, rr);
-      bf16_t* pk = a.dk + (long)(kv_off + key) * a.ld_dk + h * D;
-      bf16_t* pv = a.dv + (long)(kv_off + key) * a.ld_dv + h * D;
+      bf16_t* pk = a.dk + (long)(sd.kv_off + key) * a.ld_dk + h * D;
+      bf16_t* pv = a.dv + (long)(sd.kv_off + key) * a.ld_dv + h * D;
       if (a.wide) { store_row_wide<DB>(pk, dk, 1.f, fg); store_row_wide<DB>(pv, dv, 1.f, fg); }
       else {
 #pragma unroll
@@ -1022,13 +1042,6 @@ __global__ __launch_bounds__(256) void seq_transpose_kernel(const bf16_t* __rest
   }
 }
 
-int check_common(const AttnArgs& a, int D, int nseq, const char* who) {
-  LHRS_REQUIRE(D == 64 || D == 128, "%s: head_dim %d unsupported (64 or 128)", who, D);
-  LHRS_REQUIRE(nseq > 0 && a.H > 0, "%s: nseq=%d H=%d", who, nseq, a.H);
-  LHRS_REQUIRE(a.LTq % 64 == 0, "%s: LTq must be a multiple of 64", who);
-  return 0;
-}
-
 }  // namespace
 
 // C ABI ------------------------------------------------------------------------------------------
@@ -1048,39 +1061,66 @@ extern "C" int lhrs_seq_transpose(const void* in, long ld_in, void* out, int col
   return 0;
 }
 
+// ---- the dispatch: attn_plan.h decides, attn_run launches ----------------------------------------------------------------------------------
+using namespace attn_plan_h;
+typedef void (*AttnFn)(AttnArgs);
+#define ATTN_FNS(K) {{K<64, false>, K<64, true>}, {K<128, false>, K<128, true>}}
+// [kernel - AK_FWD_RES][D == 128][causal]; the delta kernel and the lhrs_rope passes go through their entry points
+static const AttnFn attn_fn[][2][2] = {ATTN_FNS(attn_fwd_res_kernel), ATTN_FNS(attn_fwd_kernel), ATTN_FNS(attn_bwd_dq_res_kernel),
+                                       ATTN_FNS(attn_bwd_dq_kernel), ATTN_FNS(attn_bwd_dkv_res_kernel), ATTN_FNS(attn_bwd_dkv_kernel)};
+static_assert(AK_FWD_RES == 1 && AK_FWD_TILED == 2 && AK_DQ_RES == 3 && AK_DQ_TILED == 4 && AK_DKV_RES == 5 && AK_DKV_TILED == 6 && AK_ROPE_DQ == 7,
+              "attn_fn lists the kernels in the order of AttnKernel");
+
+// One call of an entry point, which has checked its own arguments and put every pointer of the call into `call` (rope_*: the tables whenever given;
+// o_in / delta_w: lhrs_attn_bwd_o).  Validates, asks for the plan and walks it.  Host-side launches read `call`; the kernels get `seen`, a copy in
+// which the tables and o_in stay only where the plan has the rotation and delta happen inside the kernels.
+static int attn_run(int entry, const char* who, const char* who_res, const AttnArgs& call, int D, int nseq, int max_q, int max_kv, int causal,
+                    bool out_wide, long rope_rows, void* stream) {
+  LHRS_REQUIRE(D == 64 || D == 128, "%s: head_dim %d unsupported (64 or 128)", who, D);
+  LHRS_REQUIRE(nseq > 0 && call.H > 0, "%s: nseq=%d H=%d", who, nseq, call.H);
+  LHRS_REQUIRE(call.LTq % 64 == 0, "%s: LTq must be a multiple of 64", who);
+  const AttnPlan plan = attn_plan(AttnProblem{entry, D, max_q, max_kv, call.LTq, call.rope_cos != nullptr, out_wide});
+  LHRS_REQUIRE(plan.n > 0, "%s: no plan", who);
+  AttnArgs seen = call;
+  seen.wide = plan.wide;
+  if (!plan.rope_fused) seen.rope_cos = seen.rope_sin = nullptr;
+  if (!plan.delta_by_dq) seen.o_in = nullptr;
+  for (int i = 0; i < plan.n; ++i) {
+    const int k = plan.kernels[i];
+    if (k == AK_DELTA) {
+      if (lhrs_attn_delta(call.o_in, call.ld_oin, call.dout, call.ld_do, call.delta_w, call.desc, nseq, call.H, D, max_q, call.LTq, stream)) return -1;
+    } else if (k == AK_ROPE_DQ || k == AK_ROPE_DK) {  // long sequences (tiled kernels): the rotation as its own pass over the dq / dk rows, same numbers
+      if (lhrs_rope(k == AK_ROPE_DQ ? call.dq : call.dk, k == AK_ROPE_DQ ? call.ld_dq : call.ld_dk, (int)rope_rows, call.H, D, call.rope_cos, call.rope_sin,
+                    nullptr, call.rope_mod, call.rope_pos0, 1, stream))
+        return -1;
+    } else {  // resident: one 8-wave workgroup per (sequence, head); tiled: one 4-wave workgroup per 64 query (dK/dV: key) rows
+      const bool res = k == AK_FWD_RES || k == AK_DQ_RES || k == AK_DKV_RES;
+      const dim3 grid = res ? dim3(call.H, nseq) : dim3(cdiv(k == AK_DKV_TILED ? max_kv : max_q, 64), call.H, nseq);
+      hipLaunchKernelGGL(attn_fn[k - AK_FWD_RES][D == 128][causal != 0], grid, dim3(res ? 512 : 256), 0, (hipStream_t)stream, seen);
+      LHRS_CHECK_LAUNCH(res ? who_res : who);
+    }
+  }
+  return 0;
+}
+
+extern "C" int lhrs_attn_plan(int entry, int D, int max_q, int max_kv, int LTq, int has_rope, int out_wide, int* out_kernels, int cap, int* out_flags) {
+  const AttnPlan plan = attn_plan(AttnProblem{entry, D, max_q, max_kv, LTq, has_rope != 0, out_wide != 0});
+  if (plan.n < 0 || plan.n > cap) return -1;
+  for (int i = 0; i < plan.n; ++i) out_kernels[i] = plan.kernels[i];
+  *out_flags = plan.wide * 1 + plan.rope_fused * 2 + plan.delta_by_dq * 4;
+  return plan.n;
+}
+extern "C" const char* lhrs_attn_kernel_name(int kernel) { return attn_kernel_name(kernel); }
+
 static int attn_fwd_impl(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo,
                          float* lse, const int* desc, int nseq, int H, int D, int max_q, int max_kv, int LTq,
                          int causal, float scale, const unsigned char* key_mask, long ld_mask, void* stream) {
   AttnArgs a; memset(&a, 0, sizeof(a));
   a.kmask = key_mask; a.ld_kmask = ld_mask;
-  if (key_mask != nullptr) max_kv = 1 << 30;  // the mask lives in the tiled kernel only
   a.q = (const bf16_t*)q; a.ldq = ldq; a.k = (const bf16_t*)k; a.ldk = ldk; a.v = (const bf16_t*)v; a.ldv = ldv;
   a.o = (bf16_t*)o; a.ldo = ldo; a.lse = lse; a.desc = desc; a.H = H; a.LTq = LTq; a.scale = scale;
-  a.wide = (ldo % 8 == 0 && (size_t)o % 16 == 0) ? 1 : 0;
-  if (check_common(a, D, nseq, "attn_fwd")) return -1;
-  const dim3 grid(cdiv(max_q, 64), H, nseq), blk(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (max_kv > 0 && max_kv <= (D == 128 ? res_rows<128>() : res_rows<64>())) {  // both operands fit one CU's LDS
-    const dim3 rg(H, nseq), rb(512);
-    if (D == 128) {
-      if (causal) hipLaunchKernelGGL((attn_fwd_res_kernel<128, true>), rg, rb, 0, s, a);
-      else hipLaunchKernelGGL((attn_fwd_res_kernel<128, false>), rg, rb, 0, s, a);
-    } else {
-      if (causal) hipLaunchKernelGGL((attn_fwd_res_kernel<64, true>), rg, rb, 0, s, a);
-      else hipLaunchKernelGGL((attn_fwd_res_kernel<64, false>), rg, rb, 0, s, a);
-    }
-    LHRS_CHECK_LAUNCH("attn_fwd_res");
-    return 0;
-  }
-  if (D == 128) {
-    if (causal) hipLaunchKernelGGL((attn_fwd_kernel<128, true>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<128, false>), grid, blk, 0, s, a);
-  } else {
-    if (causal) hipLaunchKernelGGL((attn_fwd_kernel<64, true>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<64, false>), grid, blk, 0, s, a);
-  }
-  LHRS_CHECK_LAUNCH("attn_fwd");
-  return 0;
+  const bool out_wide = ldo % 8 == 0 && (size_t)o % 16 == 0;
+  return attn_run(key_mask ? AE_FWD_KMASK : AE_FWD, "attn_fwd", "attn_fwd_res", a, D, nseq, max_q, max_kv, causal, out_wide, 0, stream);
 }
 
 extern "C" int lhrs_attn_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo,
@@ -1115,72 +1155,28 @@ extern "C" int lhrs_attn_delta(const void* o, long ldo, const void* dout, long l
   return 0;
 }
 
-extern "C" int lhrs_rope(void* x, long ld, int rows, int nheads, int D, const float* cos_t, const float* sin_t, const int* pos_ids, int pos_mod,
-                         int pos0, int inverse, void* stream);
-
-static int attn_bwd_impl(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
+// every backward entry: o != nullptr makes delta an OUTPUT (lhrs_attn_bwd_o), rope_cos != nullptr asks for the inverse rotation of dq / dk
+static int attn_bwd_impl(int entry, const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
                          const void* dout, long ld_do, const float* lse, const float* delta, void* dq, long ld_dq,
                          void* dk, long ld_dk, void* dv, long ld_dv, const int* desc, int nseq, int H, int D,
                          int max_q, int max_kv, int LTq, int causal, float scale, const float* rope_cos, const float* rope_sin,
                          int rope_mod, int rope_pos0, long rope_rows, void* stream, const void* o = nullptr, long ldo = 0) {
   AttnArgs a; memset(&a, 0, sizeof(a));
-  if (o != nullptr) {
-    // delta is an OUTPUT here: by the resident dQ kernel when it runs (it is launched in front of the dK/dV kernel), by a launch of the
-    // delta kernel otherwise
-    const int rmax0 = D == 128 ? res_rows<128>() : res_rows<64>();
-    if (max_kv <= rmax0) { a.o_in = (const bf16_t*)o; a.ld_oin = ldo; a.delta_w = const_cast<float*>(delta); }
-    else if (lhrs_attn_delta(o, ldo, dout, ld_do, const_cast<float*>(delta), desc, nseq, H, D, max_q, LTq, stream)) return -1;
-  }
-  const bool rope = rope_cos != nullptr;
-  const int rmax_ = D == 128 ? res_rows<128>() : res_rows<64>();
-  // the resident dK/dV kernel keeps lse | delta of the sequence behind its Q image (rows rounded up to 32): head_dim 128 up to 288 queries
-  const bool dkv_fits = max_q <= rmax_ && (long)((max_q + 31) / 32 * 32) * D * 2 + 2L * LTq * 4 <= (long)rmax_ * D * 2;
-  const bool fuse_rope = rope && max_kv <= rmax_ && dkv_fits;  // both resident kernels run: the rotation rides in their stores
-  if (fuse_rope) { a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.rope_mod = rope_mod; a.rope_pos0 = rope_pos0; }
+  if (o != nullptr) { a.o_in = (const bf16_t*)o; a.ld_oin = ldo; a.delta_w = const_cast<float*>(delta); }
+  if (rope_cos != nullptr) { a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.rope_mod = rope_mod; a.rope_pos0 = rope_pos0; }
   a.q = (const bf16_t*)q; a.ldq = ldq; a.k = (const bf16_t*)k; a.ldk = ldk; a.v = (const bf16_t*)v; a.ldv = ldv;
   a.dout = (const bf16_t*)dout; a.ld_do = ld_do; a.lse = (float*)lse; a.delta = delta;
   a.dq = (bf16_t*)dq; a.ld_dq = ld_dq; a.dk = (bf16_t*)dk; a.ld_dk = ld_dk; a.dv = (bf16_t*)dv; a.ld_dv = ld_dv;
   a.desc = desc; a.H = H; a.LTq = LTq; a.scale = scale;
-  a.wide = (ld_dq % 8 == 0 && ld_dk % 8 == 0 && ld_dv % 8 == 0 && ((size_t)dq | (size_t)dk | (size_t)dv) % 16 == 0) ? 1 : 0;
-  if (check_common(a, D, nseq, "attn_bwd")) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 gq(cdiv(max_q, 64), H, nseq), gk(cdiv(max_kv, 64), H, nseq), blk(256);
-  const int rmax = D == 128 ? res_rows<128>() : res_rows<64>();
-  const dim3 rg(H, nseq), rb(512);
-  bool dq_done = false, dkv_done = false;
-  if (max_kv <= rmax) {
-    if (D == 128) { if (causal) hipLaunchKernelGGL((attn_bwd_dq_res_kernel<128, true>), rg, rb, 0, s, a); else hipLaunchKernelGGL((attn_bwd_dq_res_kernel<128, false>), rg, rb, 0, s, a); }
-    else { if (causal) hipLaunchKernelGGL((attn_bwd_dq_res_kernel<64, true>), rg, rb, 0, s, a); else hipLaunchKernelGGL((attn_bwd_dq_res_kernel<64, false>), rg, rb, 0, s, a); }
-    dq_done = true;
-  }
-  if (dkv_fits) {
-    if (D == 128) { if (causal) hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<128, true>), rg, rb, 0, s, a); else hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<128, false>), rg, rb, 0, s, a); }
-    else { if (causal) hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<64, true>), rg, rb, 0, s, a); else hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<64, false>), rg, rb, 0, s, a); }
-    dkv_done = true;
-  }
-  if (dq_done && dkv_done) { LHRS_CHECK_LAUNCH("attn_bwd_res"); return 0; }
-  // (never reached with fuse_rope: it requires both resident kernels)
-#define LAUNCH_TILED(KERN, GRID)                                                                 \
-  do {                                                                                           \
-    if (D == 128) { if (causal) hipLaunchKernelGGL((KERN<128, true>), GRID, blk, 0, s, a); else hipLaunchKernelGGL((KERN<128, false>), GRID, blk, 0, s, a); } \
-    else { if (causal) hipLaunchKernelGGL((KERN<64, true>), GRID, blk, 0, s, a); else hipLaunchKernelGGL((KERN<64, false>), GRID, blk, 0, s, a); }          \
-  } while (0)
-  if (!dq_done) LAUNCH_TILED(attn_bwd_dq_kernel, gq);
-  if (!dkv_done) LAUNCH_TILED(attn_bwd_dkv_kernel, gk);
-#undef LAUNCH_TILED
-  LHRS_CHECK_LAUNCH("attn_bwd");
-  if (rope) {  // long sequences (tiled kernels): the rotation as its own pass over the dq and dk rows, same numbers
-    if (lhrs_rope(dq, ld_dq, (int)rope_rows, H, D, rope_cos, rope_sin, nullptr, rope_mod, rope_pos0, 1, stream)) return -1;
-    if (lhrs_rope(dk, ld_dk, (int)rope_rows, H, D, rope_cos, rope_sin, nullptr, rope_mod, rope_pos0, 1, stream)) return -1;
-  }
-  return 0;
+  const bool out_wide = ld_dq % 8 == 0 && ld_dk % 8 == 0 && ld_dv % 8 == 0 && ((size_t)dq | (size_t)dk | (size_t)dv) % 16 == 0;
+  return attn_run(entry, "attn_bwd", "attn_bwd_res", a, D, nseq, max_q, max_kv, causal, out_wide, rope_rows, stream);
 }
 
 extern "C" int lhrs_attn_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
                              const void* dout, long ld_do, const float* lse, const float* delta, void* dq, long ld_dq,
                              void* dk, long ld_dk, void* dv, long ld_dv, const int* desc, int nseq, int H, int D,
                              int max_q, int max_kv, int LTq, int causal, float scale, void* stream) {
-  return attn_bwd_impl(q, ldq, k, ldk, v, ldv, dout, ld_do, lse, delta, dq, ld_dq, dk, ld_dk, dv, ld_dv, desc, nseq, H, D, max_q, max_kv, LTq,
+  return attn_bwd_impl(AE_BWD, q, ldq, k, ldk, v, ldv, dout, ld_do, lse, delta, dq, ld_dq, dk, ld_dk, dv, ld_dv, desc, nseq, H, D, max_q, max_kv, LTq,
                        causal, scale, nullptr, nullptr, 1, 0, 0, stream);
 }
 
@@ -1193,7 +1189,7 @@ extern "C" int lhrs_attn_bwd_rope(const void* q, long ldq, const void* k, long l
                                   int max_q, int max_kv, int LTq, int causal, float scale, const float* cos_t, const float* sin_t,
                                   int pos_mod, int pos0, long rows, void* stream) {
   LHRS_REQUIRE(cos_t && sin_t && pos_mod > 0 && rows > 0, "attn_bwd_rope: cos/sin tables, pos_mod=%d, rows=%ld", pos_mod, rows);
-  return attn_bwd_impl(q, ldq, k, ldk, v, ldv, dout, ld_do, lse, delta, dq, ld_dq, dk, ld_dk, dv, ld_dv, desc, nseq, H, D, max_q, max_kv, LTq,
+  return attn_bwd_impl(AE_BWD_ROPE, q, ldq, k, ldk, v, ldv, dout, ld_do, lse, delta, dq, ld_dq, dk, ld_dk, dv, ld_dv, desc, nseq, H, D, max_q, max_kv, LTq,
                        causal, scale, cos_t, sin_t, pos_mod, pos0, rows, stream);
 }
 
@@ -1206,6 +1202,6 @@ extern "C" int lhrs_attn_bwd_o(const void* q, long ldq, const void* k, long ldk,
                                float scale, const float* cos_t, const float* sin_t, int pos_mod, int pos0, long rows, void* stream) {
   LHRS_REQUIRE(o != nullptr && delta != nullptr, "attn_bwd_o: o=%p delta=%p", o, (void*)delta);
   LHRS_REQUIRE(cos_t == nullptr || (sin_t && pos_mod > 0 && rows > 0), "attn_bwd_o: cos/sin tables, pos_mod=%d, rows=%ld", pos_mod, rows);
-  return attn_bwd_impl(q, ldq, k, ldk, v, ldv, dout, ld_do, lse, delta, dq, ld_dq, dk, ld_dk, dv, ld_dv, desc, nseq, H, D, max_q, max_kv, LTq,
-                       causal, scale, cos_t, sin_t, cos_t ? pos_mod : 1, cos_t ? pos0 : 0, cos_t ? rows : 0, stream, o, ldo);
+  return attn_bwd_impl(AE_BWD_O, q, ldq, k, ldk, v, ldv, dout, ld_do, lse, delta, dq, ld_dq, dk, ld_dk, dv, ld_dv, desc, nseq, H, D, max_q, max_kv, LTq,
+                       causal, scale, cos_t, sin_t, pos_mod, pos0, rows, stream, o, ldo);
 }

@@ -5,7 +5,7 @@ from collections import namedtuple
 
 import torch
 
-# res_rows<D>() = 163840 / (2 * D * 2) (attention.hip:523): the rows of ONE operand matrix that the resident kernels keep in the LDS
+# attn_res_rows(D) = 163840 / (2 * D * 2) (csrc/attn_plan.h): the rows of ONE operand matrix that the resident kernels keep in the LDS
 RES_ROWS = {64: 640, 128: 320}
 
 # Bounds per output: (rel-L2 of one (sequence, head) cell, max |got - want| of the cell / max |want| of the cell).  Worst values measured on
@@ -34,18 +34,18 @@ def ceil32(n):
 
 
 def path_of(D, max_q, max_kv, LTq, rope=False, bwd_o=False, key_mask=False, strides=(), ptrs=()):
-    """The host dispatch of attn_fwd_impl / attn_bwd_impl (attention.hip) restated: which forward, dQ and dK/dV kernel runs ('res' | 'tiled'),
+    """The host dispatch of csrc/attn_plan.h (attn_plan, which attention.hip runs and lhrs_attn_plan exports) restated: which forward, dQ and dK/dV kernel runs ('res' | 'tiled'),
     where the inverse RoPE happens ('none' | 'fused' into the resident stores | 'separate' lhrs_rope pass), where delta comes from ('input':
     lhrs_attn_bwd reads it | 'dq_res': lhrs_attn_bwd_o, written by the resident dQ kernel | 'delta_kernel': lhrs_attn_bwd_o, a launch of
     attn_delta_kernel first) and whether result rows leave as 16-byte stores.  strides / ptrs: of the outputs the call writes."""
     R = RES_ROWS[D]
-    fwd = "res" if not key_mask and 0 < max_kv <= R else "tiled"                        # attention.hip:1054, 1061
-    dq = "res" if max_kv <= R else "tiled"                                               # attention.hip:1147
-    dkv_fits = max_q <= R and ceil32(max_q) * D * 2 + 2 * LTq * 4 <= R * D * 2           # attention.hip:1133
-    dkv = "res" if dkv_fits else "tiled"                                                 # attention.hip:1152
-    rope_mode = "none" if not rope else ("fused" if dq == "res" and dkv == "res" else "separate")   # attention.hip:1134, 1168
-    delta = "input" if not bwd_o else ("dq_res" if max_kv <= R else "delta_kernel")      # attention.hip:1127
-    wide = int(all(s % 8 == 0 for s in strides) and all(p % 16 == 0 for p in ptrs))      # attention.hip:1057, 1140
+    fwd = "res" if not key_mask and 0 < max_kv <= R else "tiled"                        # attn_plan: the forward rule (key mask: tiled only)
+    dq = "res" if max_kv <= R else "tiled"                                               # attn_plan: dq_res
+    dkv_fits = max_q <= R and ceil32(max_q) * D * 2 + 2 * LTq * 4 <= R * D * 2           # attn_plan: dkv_res (the dkv_fits expression)
+    dkv = "res" if dkv_fits else "tiled"                                                 # attn_plan: dkv_res
+    rope_mode = "none" if not rope else ("fused" if dq == "res" and dkv == "res" else "separate")   # attn_plan: rope_fused, else the two lhrs_rope passes
+    delta = "input" if not bwd_o else ("dq_res" if max_kv <= R else "delta_kernel")      # attn_plan: delta_by_dq, else the delta kernel first
+    wide = int(all(s % 8 == 0 for s in strides) and all(p % 16 == 0 for p in ptrs))      # the entry points' out_wide (attention.hip)
     return Path(fwd, dq, dkv, rope_mode, delta, wide)
 
 
