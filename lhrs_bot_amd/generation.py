@@ -1,6 +1,7 @@
 """Single-token decoding and generation for `TextModal` (text.py binds the functions below under their `TextModal` names): FORMATS, the one
 table of what `generate(weights=...)` can stream; PrefixCache, the KV cache of a conversation kept between calls; DecodeSession, the static
 buffers and launch list of one single-token step; the token loops."""
+import contextlib
 import dataclasses
 import math
 import os
@@ -590,6 +591,217 @@ def warp_logits(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[
     return z
 
 
+
+# ------------------------------------------------------------------------------------------------- the request of one generate() call
+@dataclasses.dataclass(frozen=True)
+class GenRequest:
+    """What one `generate()` call has decided before anything is allocated, merged or changed: the keywords as resolved by `resolve_request`
+    (which also makes every rejection of the call, once), and the facts derived from them.  The token loops read nothing else."""
+    m: object
+    input_ids: torch.Tensor
+    image_embedding: Optional[torch.Tensor]   # with a prefix cache and no embedding of the call's own: the cached one
+    attention_mask: Optional[torch.Tensor]
+    do_sample: bool
+    temperature: float
+    top_p: Optional[float]                    # "default" resolved, as top_k
+    top_k: Optional[int]
+    max_new_tokens: int
+    stopping_criteria: Optional[list]
+    streamer: object
+    eos_token_id: Optional[int]               # "default" resolved: the tokenizer's, None under a constraint
+    return_logits: bool
+    use_graph: bool
+    weights: str
+    seed: Optional[int]                       # of the device pick (`torch.initial_seed()` for None); None without it
+    length_penalty: float
+    early_stopping: bool
+    return_beam_scores: bool
+    kv_cache: str                             # with a prefix cache: the kind of that cache
+    prefix_cache: Optional[PrefixCache]
+    constraint: Optional[TokenAutomaton]
+    return_choices: bool
+    adapters: Optional[str]                   # how un-merged adapters run: "merged" | "live"; None: there are none, or `generate_rows` was called itself
+    pen: float                                # repetition_penalty
+    nb: int                                   # num_beams
+    device_pick: bool                         # every pick is `hk.sample_rows`: sampler="device" when sampling, or a penalty
+    host_checks: bool                         # the host looks at every token: eos / stopping criteria / streamer
+    kv8: bool
+    live_lora: bool
+    prompt: Optional[list]                    # with a prefix cache: the prompt in placeholder form, as `PrefixCache.check` returned it
+
+    lora = property(lambda self: self.m.lora if self.live_lora else None)   # adapters="live": the store the session and the GEMM steps read
+
+
+def resolve_request(m, kw, rows=False) -> GenRequest:
+    """kw: the keywords of a keyword entry point by name -> the request.  rows: the entry point is `generate_rows`, which has no `adapters`
+    keyword - the weights are left as they are and its `live_lora` says whether the adapter store is read; `TextModal.generate` has no
+    `live_lora`.  Every rejection of the call is made here, once and in this order: adapters, constraint, prefix cache, KV cache, int8 without
+    its base, sampler, beams, 4bit / int8 on merged copies.  (`DecodeSession` keeps its own checks: it is an entry point too.)"""
+    k = dict(kw)
+    adapters, pc, nb, B = None if rows else k["adapters"], k["prefix_cache"], int(k["num_beams"]), int(k["input_ids"].shape[0])
+    if not rows and adapters not in ("merged", "live"):
+        raise ValueError(f"adapters={adapters!r}: expected 'merged' or 'live'")
+    check_constraint(m, k["constraint"], k["return_choices"], k["do_sample"], k["num_beams"], k["repetition_penalty"], pc)
+    if k["constraint"] is not None and k["eos_token_id"] == "default":
+        k["eos_token_id"] = None
+    k["prompt"] = None
+    if pc is not None:
+        if k["image_embedding"] is None:
+            k["image_embedding"] = pc.image_embedding
+        emb = k["image_embedding"]
+        k["prompt"] = pc.check(m, k["input_ids"], k["attention_mask"], k["num_beams"], k["kv_cache"], k["max_new_tokens"], None if emb is None else emb.shape[1])
+        k["kv_cache"] = pc.kv_cache
+    elif k["kv_cache"] is None:
+        k["kv_cache"] = "bf16"
+    m._check_kv_cache(k["kv_cache"], B * max(nb, 1), max(nb, 1))
+    if int8_gemm(k["weights"]) and not m.base_int8:
+        raise ValueError(NO_BASE["int8"][0])
+    if k["sampler"] not in ("torch", "device"):
+        raise ValueError(f"sampler={k['sampler']!r}: expected 'torch' or 'device'")
+    for bad, why in () if nb == 1 else (
+                     (nb < 1, f"num_beams={k['num_beams']!r}: must be >= 1"),
+                     (k["do_sample"], "do_sample=True with num_beams > 1 (beam-multinomial sampling) is not implemented"),
+                     (k["streamer"] is not None, "streamer is not supported with num_beams > 1 (HF: beam search has no token stream)"),
+                     (k["stopping_criteria"] is not None, "stopping_criteria is not supported with num_beams > 1: stopping is eos_token_id / max_new_tokens, on the device"),
+                     (int(k["num_return_sequences"]) != 1, f"num_return_sequences={k['num_return_sequences']!r}: only the best hypothesis of each row is returned"),
+                     (k["early_stopping"] not in (False, True), f"early_stopping={k['early_stopping']!r}: False or True ('never' is not implemented)"),
+                     (nb > 8 or B * nb > 16, f"num_beams={nb} with batch {B}: batch * num_beams must be <= 16 (and num_beams <= 8)")):
+        if bad:
+            raise ValueError(why)
+    if m.lora is None:
+        adapters = None
+    elif adapters == "merged" and k["weights"] in ("4bit", "int8"):
+        raise ValueError(MERGED_COPIES[k["weights"]])
+    if k["eos_token_id"] == "default":
+        k["eos_token_id"] = getattr(m.tokenizer, "eos_token_id", None)
+    # sampling defaults of the reference's callers: HF GenerationConfig top_k = 50 and the Llama-2 generation_config.json top_p = 0.9
+    # apply when the caller (cli_qa.py:176-186 passes only temperature) does not say otherwise
+    for name, default in (("top_k", 50), ("top_p", 0.9)):
+        if k[name] == "default":
+            k[name] = default if k["do_sample"] else None
+    pen = float(k["repetition_penalty"])
+    device_pick = (k["sampler"] == "device" and bool(k["do_sample"])) or pen != 1.0
+    if device_pick:
+        k["seed"] = int(torch.initial_seed() if k["seed"] is None else k["seed"])
+    k.update(m=m, adapters=adapters, pen=pen, nb=nb, device_pick=device_pick, kv8=k["kv_cache"] == "fp8",
+             live_lora=bool(k["live_lora"]) if rows else adapters == "live",
+             host_checks=k["eos_token_id"] is not None or k["stopping_criteria"] is not None or k["streamer"] is not None)
+    return GenRequest(**{f.name: k[f.name] for f in dataclasses.fields(GenRequest)})
+
+
+MERGED_COPIES = {  # weights -> text of generate(weights=..., adapters="merged") with un-merged adapters
+    "4bit": 'weights="4bit" with un-merged LoRA adapters: generate() then runs on merged 16-bit COPIES, which have no 4-bit form - '
+            'call merge_lora() first (it re-quantises the merged weights, as peft does for a merged Linear4bit), or pass '
+            'adapters="live" (the adapters then run next to the 4-bit codes)',
+    "int8": 'weights="int8" with un-merged LoRA adapters: generate() then runs on merged 16-bit COPIES, which have no int8 form - '
+            'call merge_lora() first (it re-quantises the merged weights), or pass adapters="live" (the adapters then run '
+            'next to the int8 rows)'}
+
+
+def run_request(req):
+    """the resolved call, on the weights its `adapters` mode asks for (`TextModal._adapters_on`)"""
+    with req.m._adapters_on(req.adapters, req.weights):
+        return (generate_beam if req.nb != 1 else generate_tokens)(req)
+
+
+# ------------------------------------------------------------------------------------------------- what the loops share
+@contextlib.contextmanager
+def side_stream(device):
+    """the launches of the body run on a side stream behind everything queued so far (graph capture needs a non-default stream); the
+    current stream waits for them afterwards"""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        yield
+    torch.cuda.current_stream().wait_stream(side)
+
+
+def open_session(req, rows, max_ctx, caches, kmask, S0):
+    """the session of the call over `rows` cache rows, its state words behind the S0 positions of the prompt and before the first token"""
+    s = req.m._decode_session(rows, max_ctx, caches, req.max_new_tokens, req.weights, kmask, req.lora, req.kv_cache)
+    s.state[0], s.state[1] = S0, 0
+    return s
+
+
+def results(*values):
+    """what a call returns: the values that are not None as a tuple - or the ids alone"""
+    out = tuple(v for v in values if v is not None)
+    return out if len(out) > 1 else out[0]
+
+
+class Picker:
+    """The pick of a non-beam call, chosen once from the request: `pick(logits, out, step_host)` -> the next ids, int64 [B] - in `out`
+    (None: a new tensor) for the arms that are one launch, a new tensor from the host multinomial, which ignores `out`.  It owns what the
+    arms keep between tokens: the `ConstraintState`, the `seen` bitmap of the penalty, the seed, and `step_dev`, the device counter of
+    emitted tokens that numbers the draws of a session (None: `step_host` does)."""
+
+    def __init__(self, req, B):
+        self.req, self.seen, self.step_dev = req, None, None
+        self.cs = hk.ConstraintState(B, req.m.device) if req.constraint is not None else None
+        if req.device_pick and req.pen != 1.0:  # bitmap of the tokens generated so far in this call (HF started from inputs_embeds: the prompt is not in it)
+            self.seen = torch.zeros((B, (req.m.vocab + 31) // 32), device=req.m.device, dtype=torch.int32)
+        P = Picker   # the arm as a plain function: a bound method kept on the object would be a reference cycle that holds device memory until the collector runs
+        self.arm = P.constrained if self.cs is not None else P.device if req.device_pick else P.multinomial if req.do_sample else P.argmax
+
+    def pick(self, logits, out, step_host):
+        return self.arm(self, logits, out, step_host)
+
+    def constrained(self, logits, out, step_host):
+        return hk.constrain_rows(logits, self.req.constraint, self.cs, out, score=self.req.return_choices)
+
+    def device(self, logits, out, step_host):   # mode 0 draws, mode 1 is the first maximum of the penalised logits
+        r = self.req
+        return hk.sample_rows(logits, out, mode=0 if r.do_sample else 1, temperature=r.temperature, top_k=r.top_k, top_p=r.top_p,
+                              repetition_penalty=r.pen, seen=self.seen, seed=r.seed, step_dev=self.step_dev, step_host=step_host)
+
+    def multinomial(self, logits, out, step_host):
+        r = self.req
+        return torch.multinomial(torch.softmax(warp_logits(logits, r.temperature, r.top_k, r.top_p), -1), 1).squeeze(1)
+
+    def argmax(self, logits, out, step_host):
+        return hk.argmax_rows(logits, out=out)
+
+
+class SessionStepper:
+    """batch <= 16: a step is a graph replay over the session's static buffers, the ids live in `s.out_ids`"""
+
+    def __init__(self, req, s):
+        self.req, self.s, self.out = req, s, s.next_ids   # out: where a one-launch pick writes
+
+    def emit(self, nxt):
+        s = self.s
+        if nxt is not s.next_ids:   # the prefill's argmax / multinomial token, a host-side pick or pad replacement: through copy_, not written there
+            s.next_ids.copy_(nxt)
+        hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, s.B, s.max_new)
+
+    def step(self, n_done):
+        step_or_replay(self.s, self.s.enqueue, self.req.use_graph, n_done)
+        return self.s.logits, 0            # the draw's step counter is the session's, on the device
+
+    def ids(self, n):
+        return self.s.out_ids[:, :n]
+
+
+class GemmStepper:
+    """batch > 16: a step is `gather_rows` + `gemm_logits` over one new position, the ids live in a Python list"""
+    out = None
+
+    def __init__(self, req, B, S0, max_ctx, caches, kmask):
+        self.req, self.B, self.S0, self.cache_args, self.toks = req, B, S0, (caches, max_ctx, False, kmask, req.lora, req.weights), []
+
+    def emit(self, nxt):
+        self.toks.append(nxt)
+
+    def step(self, n_done):
+        m = self.req.m
+        x = hk.gather_rows(m.p["embed"], self.toks[-1].clamp(0, m.vocab - 1).to(torch.int32))
+        return gemm_logits(m, x, self.B, 1, self.S0 + n_done - 1, *self.cache_args), n_done   # the draw's step counter is the host's
+
+    def ids(self, n):
+        return torch.stack(self.toks, 1)
+
+
+# ------------------------------------------------------------------------------------------------- the token loops
 def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p=None, top_k=None,
                   max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id=None, return_logits=False,
                   use_graph=True, weights="bf16", sampler="torch", seed=None, repetition_penalty=1.0, num_beams=1, length_penalty=1.0,
@@ -618,217 +830,129 @@ def generate_rows(m, input_ids, image_embedding=None, attention_mask=None, do_sa
     The model step, the graph and `decode_emit` are as ever.  Rows behind a final state emit pad_token_id; the host reads the rows' `fin`
     every fourth token (every token on the host path of eos / stopping criteria / streamer) and stops when all are final; the ids are cut to
     the longest row, its EOS included.  return_choices=True appends (choice [B] int64: the final state's label, -1 where max_new_tokens ran
-    out first; score [B] fp32: the sum of the picked tokens' log-probabilities over the full vocabulary) - only then is the score computed."""
-    check_constraint(m, constraint, return_choices, do_sample, num_beams, repetition_penalty, prefix_cache)
-    if sampler not in ("torch", "device"):
-        raise ValueError(f"sampler={sampler!r}: expected 'torch' or 'device'")
-    pc = prefix_cache
-    if pc is not None:   # rejections first: nothing is allocated or changed before them
-        if image_embedding is None:
-            image_embedding = pc.image_embedding
-        prompt = pc.check(m, input_ids, attention_mask, num_beams, kv_cache, max_new_tokens, None if image_embedding is None else image_embedding.shape[1])
-    if int(num_beams) != 1:
-        return m._generate_beam(input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer,
-                                eos_token_id, return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty,
-                                early_stopping, return_beam_scores, num_return_sequences, live_lora, kv_cache)
-    m._check_kv_cache(kv_cache, int(input_ids.shape[0]))
-    pen = float(repetition_penalty)
-    device_pick = (sampler == "device" and do_sample) or pen != 1.0
+    out first; score [B] fp32: the sum of the picked tokens' log-probabilities over the full vocabulary) - only then is the score computed.
+
+    A keyword entry point: the work is `resolve_request` (every rejection), then `generate_tokens` or `generate_beam` on the request."""
+    return run_request(resolve_request(m, locals(), rows=True))
+
+
+def generate_tokens(req):
+    """the non-beam call: prefill, first pick, then ONE loop of [emit, host's look, step, pick] over a `SessionStepper` or a `GemmStepper`"""
+    m, pc, dev, streamer, max_new = req.m, req.prefix_cache, req.m.device, req.streamer, req.max_new_tokens
     if streamer is not None and getattr(streamer, "skip_prompt", False):
-        streamer.put(input_ids.cpu())  # transformers.TextStreamer protocol: the first put() is the prompt, which skip_prompt drops
-    embeds, _, mask, _ = m.prepare_inputs_for_multimodal(input_ids, attention_mask, None, image_embedding)
+        streamer.put(req.input_ids.cpu())  # transformers.TextStreamer protocol: the first put() is the prompt, which skip_prompt drops
+    embeds, _, mask, _ = m.prepare_inputs_for_multimodal(req.input_ids, req.attention_mask, None, req.image_embedding)
     B, S0, d = embeds.shape
     if pc is None:
-        max_ctx, kmask = decode_context(m, mask, B, S0, max_new_tokens)
-        caches, reuse = m._alloc_kv(B * max_ctx, kv_cache), 0
+        max_ctx, kmask = decode_context(m, mask, B, S0, max_new)
+        caches, reuse = m._alloc_kv(B * max_ctx, req.kv_cache), 0
     else:   # the cache's own rows, all of them visible; it is rolled back to the reused positions before the prefill writes behind them
         max_ctx, kmask = pc.max_positions, None
-        reuse = pc.begin(prompt, image_embedding)
+        reuse = pc.begin(req.prompt, req.image_embedding)
         caches = pc.caches
-    dev, lora = m.device, m.lora if live_lora else None   # adapters="live": the store the session and the GEMM steps read
-    s, seen, step_dev = None, None, None
-    cs = hk.ConstraintState(B, dev) if constraint is not None else None
-
-    def session():
-        s = m._decode_session(B, max_ctx, caches, max_new_tokens, weights, kmask, lora, kv_cache)
-        s.state[0], s.state[1] = S0, 0
-        return s
-
-    if device_pick:
-        seed = int(torch.initial_seed() if seed is None else seed)
-        if pen != 1.0:  # bitmap of the tokens generated so far in this call (HF started from inputs_embeds: the prompt is not in it)
-            seen = torch.zeros((B, (m.vocab + 31) // 32), device=dev, dtype=torch.int32)
-        if B <= 16:  # the draw's step counter is the session's count of emitted tokens, on the device
-            s = session()
-            step_dev = s.state[1:2]
-    elif cs is not None and B <= 16:
-        s = session()
-
-    def pick_device(logits, out=None, step_host=0):
-        return hk.sample_rows(logits, out, mode=0 if do_sample else 1, temperature=temperature, top_k=top_k, top_p=top_p,
-                              repetition_penalty=pen, seen=seen, seed=seed, step_dev=step_dev, step_host=step_host)
-
-    def pick_constrained(logits, out=None):
-        return hk.constrain_rows(logits, constraint, cs, out, score=return_choices)
-
-    def pick(logits):
-        if cs is not None:
-            return pick_constrained(logits, None if s is None else s.next_ids)
-        if device_pick:
-            return pick_device(logits, None if s is None else s.next_ids, 0 if s is not None else n_done)
-        if not do_sample:
-            return hk.argmax_rows(logits)
-        return torch.multinomial(torch.softmax(warp_logits(logits, temperature, top_k, top_p), -1), 1).squeeze(1)
-
+    picker = Picker(req, B)
+    cs, one_launch_pick = picker.cs, req.device_pick or req.constraint is not None
+    # ORDER KEPT: with batch <= 16 the session is built BEFORE the prefill only for the picks that write into it (device pick, constraint) ...
+    s = open_session(req, B, max_ctx, caches, kmask, S0) if B <= 16 and one_launch_pick else None
+    if s is not None and req.device_pick:
+        picker.step_dev = s.state[1:2]
     # ---- prefill (GEMM path) -> logits of the last prompt position -> first new token
     # (behind the `reuse` positions a prefix cache already holds: B = 1, the rows of embeds[0, reuse:])
-    logits = gemm_logits(m, embeds.reshape(B * S0, d)[reuse:], B, S0 - reuse, reuse, caches, max_ctx, kv_cache == "fp8", kmask, lora, weights)
-    all_logits = [logits.clone()] if return_logits else []
-    n_done = 0
-    nxt = pick(logits)
-
-    host_checks = eos_token_id is not None or stopping_criteria is not None or streamer is not None
-    finished = torch.zeros(B, dtype=torch.bool, device=dev)
+    logits = gemm_logits(m, embeds.reshape(B * S0, d)[reuse:], B, S0 - reuse, reuse, caches, max_ctx, req.kv8, kmask, req.lora, req.weights)
+    all_logits = [logits.clone()] if req.return_logits else []
+    nxt = picker.pick(logits, None if s is None else s.next_ids, 0)
+    if B <= 16 and s is None:
+        s = open_session(req, B, max_ctx, caches, kmask, S0)   # ... and AFTER the prefill and its pick otherwise (`SessionStepper.emit` copies that token in)
+    stepper = SessionStepper(req, s) if B <= 16 else GemmStepper(req, B, S0, max_ctx, caches, kmask)
+    finished, pad = torch.zeros(B, dtype=torch.bool, device=dev), m.tokenizer.pad_token_id
 
     def host_step(ids_so_far, lg):  # -> stop?
         nonlocal finished
         if streamer is not None:
             streamer.put(ids_so_far[:, -1].cpu())
-        if eos_token_id is not None:
-            finished |= ids_so_far[:, -1] == eos_token_id
+        if req.eos_token_id is not None:
+            finished |= ids_so_far[:, -1] == req.eos_token_id
             if bool(finished.all()):
                 return True
         if cs is not None and bool(cs.fin.all()):
             return True
-        return stopping_criteria is not None and any(c(ids_so_far, lg) for c in stopping_criteria)
+        return req.stopping_criteria is not None and any(c(ids_so_far, lg) for c in req.stopping_criteria)
 
-    n_done = 1
-    if B <= 16:
-        if s is None:
-            s = session()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            if nxt is not s.next_ids:
-                s.next_ids.copy_(nxt)
-            hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, B, max_new_tokens)
-            stop = host_checks and host_step(s.out_ids[:, :1], logits)
-            while not stop and n_done < max_new_tokens:
-                step_or_replay(s, s.enqueue, use_graph, n_done)
-                if return_logits:
-                    all_logits.append(s.logits.clone())
-                if cs is not None:
-                    pick_constrained(s.logits, s.next_ids)
-                elif device_pick:
-                    pick_device(s.logits, s.next_ids)
-                elif do_sample:
-                    s.next_ids.copy_(pick(s.logits))
-                else:
-                    hk.argmax_rows(s.logits, out=s.next_ids)
-                if eos_token_id is not None:
-                    s.next_ids.copy_(torch.where(finished, torch.full_like(s.next_ids, m.tokenizer.pad_token_id), s.next_ids))
-                hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, B, max_new_tokens)
-                n_done += 1
-                if host_checks:
-                    stop = host_step(s.out_ids[:, :n_done], s.logits)
-                elif cs is not None and n_done % 4 == 0:   # as generate_beam reads its done word
-                    stop = bool(cs.fin.all())
-        torch.cuda.current_stream().wait_stream(side)
-        ids = s.out_ids[:, :n_done].clone()
-    else:
-        out_ids = [nxt]
-        stop = host_checks and host_step(torch.stack(out_ids, 1), logits)
-        while not stop and n_done < max_new_tokens:
-            x = hk.gather_rows(m.p["embed"], out_ids[-1].clamp(0, m.vocab - 1).to(torch.int32))
-            logits = gemm_logits(m, x, B, 1, S0 + n_done - 1, caches, max_ctx, False, kmask, lora, weights)
-            if return_logits:
-                all_logits.append(logits.clone())
-            nxt = pick(logits)
-            if eos_token_id is not None:
-                nxt = torch.where(finished, torch.full_like(nxt, m.tokenizer.pad_token_id), nxt)
-            out_ids.append(nxt)
+    n_done = 0
+    with side_stream(dev) if B <= 16 else contextlib.nullcontext():
+        while True:
+            stepper.emit(nxt)
             n_done += 1
-            if host_checks:
-                stop = host_step(torch.stack(out_ids, 1), logits)
-            elif cs is not None and n_done % 4 == 0:
-                stop = bool(cs.fin.all())
-        ids = torch.stack(out_ids, 1)
+            if req.host_checks:
+                stop = host_step(stepper.ids(n_done), logits)
+            else:   # as generate_beam reads its done word
+                stop = cs is not None and n_done % 4 == 0 and bool(cs.fin.all())
+            if stop or n_done >= max_new:
+                break
+            logits, step_host = stepper.step(n_done)
+            if req.return_logits:
+                all_logits.append(logits.clone())
+            nxt = picker.pick(logits, stepper.out, step_host)
+            if req.eos_token_id is not None:   # finished rows emit pads
+                nxt = torch.where(finished, torch.full_like(nxt, pad), nxt)
+    ids = stepper.ids(n_done).clone()
     if cs is not None:   # the longest row with its EOS: the columns behind it (the picks since the last look at `fin`) hold pads only
         n_done = int(cs.len.max().item())
         ids, all_logits = ids[:, :n_done].contiguous(), all_logits[:n_done]
     if pc is not None:
-        pc.commit(prompt, ids[0].tolist(), S0, reuse)
+        pc.commit(req.prompt, ids[0].tolist(), S0, reuse)
     if streamer is not None:
         streamer.end()
-    out = (ids,) + ((torch.stack(all_logits, 1),) if return_logits else ()) + ((cs.choice.to(torch.int64), cs.score.clone()) if return_choices else ())
-    return out if len(out) > 1 else out[0]
+    return results(ids, torch.stack(all_logits, 1) if req.return_logits else None,
+                   *((cs.choice.to(torch.int64), cs.score.clone()) if req.return_choices else ()))
 
 
-def generate_beam(m, input_ids, image_embedding, attention_mask, do_sample, max_new_tokens, stopping_criteria, streamer, eos_token_id,
-                  return_logits, use_graph, weights, repetition_penalty, num_beams, length_penalty, early_stopping, return_beam_scores,
-                  num_return_sequences, live_lora=False, kv_cache="bf16"):
+def generate_beam(req):
     """Deterministic beam search, HF `generate(num_beams=nb, do_sample=False)` (generation/utils.py _beam_search): the prompt is prefilled ONCE per
     batch row into cache row b * nb and replicated to the row's other beams by `hk.kv_beam_reorder`; every further token is one single-stream
     graph of [model step over B * nb rows, beam_topk_rows, beam_step, kv_beam_reorder, decode_emit] (csrc/beam.hip).  All bookkeeping lives on
     the device; the host reads the batch-wide `done` word every fourth token when an EOS is set (once done, the kernels change nothing) and never
     without one.  -> ids [B, L] of each row's best hypothesis, pad_token_id past its end (, logits [B * nb, n, V])(, scores [B])."""
-    nb = int(num_beams)
-    for bad, why in ((nb < 1, f"num_beams={num_beams!r}: must be >= 1"),
-                     (do_sample, "do_sample=True with num_beams > 1 (beam-multinomial sampling) is not implemented"),
-                     (streamer is not None, "streamer is not supported with num_beams > 1 (HF: beam search has no token stream)"),
-                     (stopping_criteria is not None, "stopping_criteria is not supported with num_beams > 1: stopping is eos_token_id / max_new_tokens, on the device"),
-                     (int(num_return_sequences) != 1, f"num_return_sequences={num_return_sequences!r}: only the best hypothesis of each row is returned"),
-                     (early_stopping not in (False, True), f"early_stopping={early_stopping!r}: False or True ('never' is not implemented)")):
-        if bad:
-            raise ValueError(why)
-    m._check_kv_cache(kv_cache, int(input_ids.shape[0]) * nb, nb)
-    embeds, _, mask, _ = m.prepare_inputs_for_multimodal(input_ids, attention_mask, None, image_embedding)
+    m, nb, max_new, dev = req.m, req.nb, req.max_new_tokens, req.m.device
+    embeds, _, mask, _ = m.prepare_inputs_for_multimodal(req.input_ids, req.attention_mask, None, req.image_embedding)
     B, S0, d = embeds.shape
     R = B * nb
-    if nb > 8 or R > 16:
-        raise ValueError(f"num_beams={nb} with batch {B}: batch * num_beams must be <= 16 (and num_beams <= 8)")
-    V, dev, pen = m.vocab, m.device, float(repetition_penalty)
-    max_ctx, kmask = decode_context(m, mask, B, S0, max_new_tokens)   # left-padded prompts, as in generate_rows; every beam hides its row's padding
+    max_ctx, kmask = decode_context(m, mask, B, S0, max_new)   # left-padded prompts, as in generate_tokens; every beam hides its row's padding
     kmask_r = None if kmask is None else kmask.repeat_interleave(nb, 0).contiguous()
-    caches = m._alloc_kv(R * max_ctx, kv_cache)
-    kv8, lora = kv_cache == "fp8", m.lora if live_lora else None
-    s = m._decode_session(R, max_ctx, caches, max_new_tokens, weights, kmask_r, lora, kv_cache)
-    s.state[0], s.state[1] = S0, 0
-    st = hk.BeamState(B, nb, V, max_new_tokens, length_penalty, dev)
+    caches = m._alloc_kv(R * max_ctx, req.kv_cache)
+    s = open_session(req, R, max_ctx, caches, kmask_r, S0)
+    st = hk.BeamState(B, nb, m.vocab, max_new, req.length_penalty, dev)
     # kv_beam_reorder is a byte copy in 16-byte chunks whose `d` counts 2-byte units: the bf16 caches with d, the kv8 code caches with d / 2
     # and the scale arrays with H / 2 - codes and scales move together, in two launches
-    tables = [(hk.kv_cache_table(caches, dev), d)] if not kv8 else [(hk.kv_cache_table([c[:2] for c in caches], dev), d // 2),
-                                                                    (hk.kv_cache_table([c[2:] for c in caches], dev), m.heads // 2)]
+    tables = [(hk.kv_cache_table(caches, dev), d)] if not req.kv8 else [(hk.kv_cache_table([c[:2] for c in caches], dev), d // 2),
+                                                                        (hk.kv_cache_table([c[2:] for c in caches], dev), m.heads // 2)]
 
     # ---- prefill: sequence b into cache row b * nb (a cache "row" of nb * max_ctx positions), logits of the last prompt position
-    logits = gemm_logits(m, embeds.reshape(B * S0, d), B, S0, 0, caches, nb * max_ctx, kv8, kmask, lora, weights)
+    logits = gemm_logits(m, embeds.reshape(B * S0, d), B, S0, 0, caches, nb * max_ctx, req.kv8, kmask, req.lora, req.weights)
     logits = logits.repeat_interleave(nb, 0).contiguous()   # the row's beams all start from it
-    all_logits = [logits] if return_logits else []
+    all_logits = [logits] if req.return_logits else []
 
     def beam_tail(lg, t0, t1):
-        hk.beam_topk_rows(lg, st, pen)
-        hk.beam_step(st, s.next_ids, eos_token_id, early_stopping)
+        hk.beam_topk_rows(lg, st, req.pen)
+        hk.beam_step(st, s.next_ids, req.eos_token_id, req.early_stopping)
         for table, units in tables:
-            hk.kv_beam_reorder(table, B, nb, max_ctx, units, st.parent, t0, t1, S0 if t0 == 0 else max_new_tokens, done=st.bstate[1:2])
-        hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, R, max_new_tokens)
+            hk.kv_beam_reorder(table, B, nb, max_ctx, units, st.parent, t0, t1, S0 if t0 == 0 else max_new, done=st.bstate[1:2])
+        hk.decode_emit(s.next_ids, s.tok32, s.out_ids, s.state, R, max_new)
 
     def step():
         s.enqueue()
         beam_tail(s.logits, S0, s.state[0:1])
 
-    side = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
+    with side_stream(dev):
         beam_tail(logits, 0, S0)          # parents are all 0: replicates the prompt's cache to every beam of the row
         n_done = 1
-        while n_done < max_new_tokens:
-            step_or_replay(s, step, use_graph, n_done)
-            if return_logits:
+        while n_done < max_new:
+            step_or_replay(s, step, req.use_graph, n_done)
+            if req.return_logits:
                 all_logits.append(s.logits.clone())
             n_done += 1
-            if eos_token_id is not None and n_done % 4 == 0 and int(st.bstate[1].item()):
+            if req.eos_token_id is not None and n_done % 4 == 0 and int(st.bstate[1].item()):
                 break
-    torch.cuda.current_stream().wait_stream(side)
     # ---- the result of each row: its best finished hypothesis, else its best running beam (tiny host-side epilogue, once per call)
     n = int(st.bstate[0].item())
     fin_score, fin_len, fin_slot = st.fin_score.view(B, nb).cpu(), st.fin_len.view(B, nb).cpu(), st.fin_slot.view(B, nb).cpu()
@@ -844,9 +968,5 @@ def generate_beam(m, input_ids, image_embedding, attention_mask, do_sample, max_
     ids = torch.full((B, max(len(r) for r in rows)), int(m.tokenizer.pad_token_id), dtype=torch.int64)
     for b, r in enumerate(rows):
         ids[b, :len(r)] = r
-    out = (ids.to(dev),)
-    if return_logits:
-        out += (torch.stack(all_logits[:n], 1),)
-    if return_beam_scores:
-        out += (torch.tensor(scores, dtype=torch.float32, device=dev),)
-    return out if len(out) > 1 else out[0]
+    return results(ids.to(dev), torch.stack(all_logits[:n], 1) if req.return_logits else None,
+                   torch.tensor(scores, dtype=torch.float32, device=dev) if req.return_beam_scores else None)

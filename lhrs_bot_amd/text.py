@@ -640,7 +640,7 @@ class TextModal:
 
     # ------------------------------------------------------------------ generate (KV cache): generation.py, bound here so that callers go through the model
     _layer_step, _check_kv_cache, _alloc_kv = generation.layer_step, generation.check_kv_cache, generation.alloc_kv
-    _generate, _generate_beam = generation.generate_rows, generation.generate_beam
+    _generate = generation.generate_rows
 
     def _decode_session(self, B, max_ctx, caches, max_new, weights="bf16", kmask=None, lora=None, kv_cache="bf16"):
         return generation.DecodeSession(self, B, max_ctx, caches, max_new, weights, kmask, lora, kv_cache)
@@ -767,6 +767,24 @@ class TextModal:
         finally:
             self.base, self.p["layers"] = saved
 
+    @contextlib.contextmanager
+    def _adapters_on(self, adapters, weights):
+        """generate() with un-merged adapters (`adapters` None: there are none): "live" - nothing is merged or swapped, the bf16 base weights
+        serve prefill, `weights` picks the decode stream, dropout is off; "merged" - merged 16-bit copies (no 8-bit operands of them exist)"""
+        if adapters is None:
+            yield
+        elif adapters == "live":
+            lo = self.lora
+            train, lo.train_mode = lo.train_mode, False
+            try:
+                with self._decoding_on(weights):
+                    yield
+            finally:
+                lo.train_mode = train
+        else:
+            with self._decoding_on(weights, self._lora_merged_layers()):
+                yield
+
     @torch.no_grad()
     def generate(self, input_ids, image_embedding=None, attention_mask=None, do_sample=False, temperature=1.0, top_p="default",
                  top_k="default", max_new_tokens=512, use_cache=True, stopping_criteria=None, streamer=None, eos_token_id="default",
@@ -816,55 +834,7 @@ class TextModal:
         do_sample, num_beams != 1, repetition_penalty != 1 and prefix_cache raise ValueError, as does an automaton of another vocabulary
         size or device.  `return_choices=True` appends (choice [B] int64 - the label of the final state, -1 where max_new_tokens ran out
         first -, score [B] fp32 - the sum of the picked tokens' log-probabilities, normalised over the full vocabulary as HF's scores are)."""
-        if adapters not in ("merged", "live"):
-            raise ValueError(f"adapters={adapters!r}: expected 'merged' or 'live'")
-        generation.check_constraint(self, constraint, return_choices, do_sample, num_beams, repetition_penalty, prefix_cache)
-        if constraint is not None and eos_token_id == "default":
-            eos_token_id = None
-        if prefix_cache is not None:   # before anything is allocated (the merged copies below) or changed
-            emb = image_embedding if image_embedding is not None else prefix_cache.image_embedding
-            prefix_cache.check(self, input_ids, attention_mask, num_beams, kv_cache, max_new_tokens, None if emb is None else emb.shape[1])
-            kv_cache = prefix_cache.kv_cache
-        elif kv_cache is None:
-            kv_cache = "bf16"
-        nb_ = int(num_beams) if int(num_beams) >= 1 else 1
-        self._check_kv_cache(kv_cache, int(input_ids.shape[0]) * nb_, nb_)
-        if eos_token_id == "default":
-            eos_token_id = getattr(self.tokenizer, "eos_token_id", None)
-        # sampling defaults of the reference's callers: HF GenerationConfig top_k = 50 and the Llama-2 generation_config.json top_p = 0.9
-        # apply when the caller (cli_qa.py:176-186 passes only temperature) does not say otherwise
-        if top_k == "default":
-            top_k = 50 if do_sample else None
-        if top_p == "default":
-            top_p = 0.9 if do_sample else None
-        kw = dict(image_embedding=image_embedding, attention_mask=attention_mask, do_sample=do_sample, temperature=temperature, top_p=top_p,
-                  top_k=top_k, max_new_tokens=max_new_tokens, use_cache=use_cache, stopping_criteria=stopping_criteria, streamer=streamer,
-                  eos_token_id=eos_token_id, return_logits=return_logits, use_graph=use_graph, weights=weights, sampler=sampler, seed=seed,
-                  repetition_penalty=repetition_penalty, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
-                  return_beam_scores=return_beam_scores, num_return_sequences=_kw.get("num_return_sequences", 1), kv_cache=kv_cache, prefix_cache=prefix_cache,
-                  constraint=constraint, return_choices=return_choices)
-        if generation.int8_gemm(weights) and not self.base_int8:
-            raise ValueError(generation.NO_BASE["int8"][0])
-        if self.lora is None:
-            return self._generate(input_ids, **kw)
-        if adapters == "live":   # nothing is merged or swapped: the bf16 base weights serve prefill, `weights` picks the decode stream, dropout is off
-            lo = self.lora
-            train, lo.train_mode = lo.train_mode, False
-            try:
-                with self._decoding_on(weights):
-                    return self._generate(input_ids, live_lora=True, **kw)
-            finally:
-                lo.train_mode = train
-        if weights == "4bit":
-            raise ValueError('weights="4bit" with un-merged LoRA adapters: generate() then runs on merged 16-bit COPIES, which have no 4-bit form - '
-                             'call merge_lora() first (it re-quantises the merged weights, as peft does for a merged Linear4bit), or pass '
-                             'adapters="live" (the adapters then run next to the 4-bit codes)')
-        if weights == "int8":
-            raise ValueError('weights="int8" with un-merged LoRA adapters: generate() then runs on merged 16-bit COPIES, which have no int8 form - '
-                             'call merge_lora() first (it re-quantises the merged weights), or pass adapters="live" (the adapters then run '
-                             'next to the int8 rows)')
-        with self._decoding_on(weights, self._lora_merged_layers()):   # merged 16-bit copies: no 8-bit operands of them exist
-            return self._generate(input_ids, **kw)
+        return generation.run_request(generation.resolve_request(self, {**locals(), "num_return_sequences": _kw.get("num_return_sequences", 1)}))
 
     # ------------------------------------------------------------------ backward (activation gradients only)
     def backward(self, loss_scale: float = 1.0, need_input_grad: bool = True, on_layer_ready=None):

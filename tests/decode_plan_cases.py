@@ -10,7 +10,15 @@ ordinal of the storage's first appearance in the trace: the ping-pong of the hid
 without naming an attribute of the session.  Raw addresses (`copy_2d`) become `<owner>@<byte offset>`.
 
 tests/golden/decode_plan.json holds, per case, the call names and the SHA-256 of the canonical trace (tests/golden/make_golden_decode_plan.py);
-tests/test_decode_plan_cpu.py compares.  A host-side refactor of the decode path must leave every digest as it is."""
+tests/test_decode_plan_cpu.py compares.  A host-side refactor of the decode path must leave every digest as it is.
+
+The cases `generate/...` record whole `TextModal.generate` calls: the picks hand back zero-filled int64 (no row ever finishes by accident),
+`hk.HipGraph` is a class that launches nothing and records `HipGraph.begin` / `.end` / `.launch` as calls of their own, and the
+side-stream bracket of generation.py is a null context.  With max_new_tokens=5 a session loop is one eager step, one capture, replays.
+Their golden entries were recorded on the commit before the token loops became one, where the bracket was still inline: there
+`_no_side_stream` replaced `torch.cuda.Stream`, `torch.cuda.stream` and `torch.cuda.current_stream` by no-ops instead of `G.side_stream`;
+nothing else of this file differed.  The trace holds `hk` calls only: that the prefill's argmax / multinomial token reaches `s.next_ids`
+through `copy_` (a torch call) is not seen here - tests/test_generate_trace_gpu.py holds the tokens that depend on it."""
 import contextlib
 import hashlib
 import inspect
@@ -19,8 +27,9 @@ import os
 
 import torch
 
+import lhrs_bot_amd.generation as G
 import lhrs_bot_amd.kernels as hk
-from lhrs_bot_amd.text import LORA_ALL, TextModal
+from lhrs_bot_amd.text import IMAGE_TOKEN_INDEX, LORA_ALL, TextModal
 
 # pure functions of shapes: they stay what they are.  `lora_down_splits` asks liblhrs_hip.so, so the BUILT library is required (no GPU is):
 # without it every case with an adapter store, and the golden maker, end in the loader's RuntimeError
@@ -73,8 +82,8 @@ def _returns(name, a):
         return (h, q) if name == "rmsnorm_fwd_q" else (h, q[0], q[1])
     if name == "swiglu_fwd":
         return out if out is not None else _E((a["gate_up"].shape[0], a["F"]))
-    if name in ("gemm_nt", "gemm_nt_lora"):
-        return out if out is not None else _E((a["a"].shape[0], a["b"].shape[0]), F32 if a["out_f32"] else BF)
+    if name in ("gemm_nt", "gemm_nt_lora"):   # fp32 without `out`: logits the host may read (warp_logits + multinomial) - zeros
+        return out if out is not None else (torch.zeros if a["out_f32"] else _E)((a["a"].shape[0], a["b"].shape[0]), dtype=F32 if a["out_f32"] else BF)
     if name == "gemm_nt_skinny":
         return _E((a["a"].shape[0], a["b"].shape[0]))
     if name == "gemm_rope_fwd":
@@ -87,6 +96,26 @@ def _returns(name, a):
         return out if out is not None else _E((a["idx"].numel(), a["src"].shape[1]), a["src"].dtype)
     if name == "lora_down":
         return REAL_FNS["lora_down_splits"](a["K"], a["A"].shape[0] if a["R"] is None else int(a["R"]))
+    if name in ("argmax_rows", "sample_rows", "constrain_rows"):   # the picks: token 0 for every row
+        return out if out is not None else torch.zeros(a["logits_f32"].shape[0], dtype=torch.int64)
+    if name == "h2d":
+        return a["t"]
+    if name == "make_desc":
+        return torch.zeros((len(a["entries"]), 8), dtype=torch.int32)
+    if name == "kv_cache_table":
+        return torch.zeros(sum(len(kv) for kv in a["caches"]), dtype=torch.int64)
+    if name == "splice_map_fwd":
+        return _E((a["ids"].shape[0], a["S"], a["image"].shape[-1]))
+    if name == "splice_fwd":   # -> (embeds, labels, mask, img_pos); the mask is the real one (the image block is visible): it decides the key mask
+        ids, mask, S = a["ids"], a["mask"], a["S"]
+        B, T = ids.shape
+        rows = []
+        for b in range(B):
+            mrow = torch.ones(T, dtype=U8) if mask is None else mask[b].to(U8)
+            pos = (ids[b] == IMAGE_TOKEN_INDEX).nonzero()
+            p = int(pos[0]) if len(pos) else T
+            rows.append(torch.cat([mrow[:p], torch.ones(S - T + 1 if p < T else 0, dtype=U8), mrow[p + 1:], torch.zeros(0 if p < T else S - T, dtype=U8)]))
+        return _E((B, S, a["image"].shape[2])), torch.zeros((B, S), dtype=torch.int64), torch.stack(rows), torch.zeros(B, dtype=torch.int32)
     if "out" in a and out is None:
         raise NotImplementedError(f"decode_plan_cases: no return rule for hk.{name} without `out`")
     return out
@@ -111,6 +140,12 @@ class Recorder:
     def __init__(self):
         self.calls, self.keep = [], []
 
+    def _graph_class(rec):
+        class NoLaunchGraph:
+            """`hk.HipGraph` without capture or replay: begin / end / launch are entries of the trace"""
+            begin, end, launch = (lambda self, n=n: rec.calls.append((n, {})) for n in ("HipGraph.begin", "HipGraph.end", "HipGraph.launch"))
+        return NoLaunchGraph
+
     def _stub(self, name):
         sig = SIGNATURES[name]
 
@@ -127,10 +162,10 @@ class Recorder:
 
     @contextlib.contextmanager
     def installed(self):
-        saved = {n: getattr(hk, n) for n in PUBLIC + ["BatchedTranspose"]}
+        saved = {n: getattr(hk, n) for n in PUBLIC + ["BatchedTranspose", "HipGraph"]}
         for n in PUBLIC:
             setattr(hk, n, self._stub(n))
-        hk.BatchedTranspose = _NoLaunchTranspose
+        hk.BatchedTranspose, hk.HipGraph = _NoLaunchTranspose, self._graph_class()
         try:
             yield self
         finally:
@@ -218,7 +253,7 @@ class Recorder:
                 return {str(k): canon(v) for k, v in sorted(o.items(), key=lambda kv: str(kv[0]))}
             if isinstance(o, (list, tuple)):
                 return [canon(v) for v in o]
-            if hasattr(o, "__dict__") and type(o).__module__ == hk.__name__:
+            if hasattr(o, "__dict__") and (type(o).__module__ == hk.__name__ or isinstance(o, G.TokenAutomaton)):
                 return {type(o).__name__: canon({k: v for k, v in vars(o).items() if not k.startswith("_")})}
             raise TypeError(f"decode_plan_cases: cannot canonicalise {type(o)}")
 
@@ -327,6 +362,105 @@ def generate_reject_case(weights):
     return fn
 
 
+@contextlib.contextmanager
+def _no_side_stream():
+    """the side-stream bracket of the token loops as a null context (there is no stream on the CPU)"""
+    saved, G.side_stream = G.side_stream, lambda device: contextlib.nullcontext()
+    try:
+        yield
+    finally:
+        G.side_stream = saved
+
+
+class _Streamer:
+    put = end = lambda self, *a: None
+
+
+NEW, NI = 5, 4   # one eager step, one capture, replays; the image block behind the placeholder
+
+
+def generate_case(B=2, calls=1, pad=False, seed=None, constraint=False, prefix_cache=None, heads=2, dim=256, base=None, lora=None, **kw):
+    """`calls` whole generate() calls on a prompt of 6 ids with one <image> placeholder; constraint: a three-choice automaton;
+    prefix_cache: the kv_cache of a PrefixCache that the calls share (the second prompt continues the first)"""
+    def fn(rec):
+        m = model(heads=heads, dim=dim, base=base, lora=lora)
+        ids = torch.arange(3, 3 + B * 6).reshape(B, 6) % 100 + 3
+        ids[:, 0], ids[:, 1] = 1, IMAGE_TOKEN_INDEX
+        mask = None
+        if pad:
+            mask = torch.ones((B, 6), dtype=torch.int64)
+            ids[0, 2:] = ids[0, :4].clone()
+            ids[0, :2], mask[0, :2] = 0, 0
+        image = torch.zeros((B, NI, dim), dtype=BF)
+        opts = {"eos_token_id": None, **kw}
+        if constraint:
+            opts["constraint"] = G.choice_automaton([[5, 6], [5, 7, 8], [9]], 2, 0, m.vocab)
+        if prefix_cache:
+            opts["prefix_cache"] = m.new_prefix_cache(prefix_cache, 64)
+        rec.keep += [ids, image, mask, opts]
+        rec.reset()
+        if seed is not None:
+            torch.manual_seed(seed)
+        with _no_side_stream():
+            for i in range(calls):
+                out = m.generate(ids, None if prefix_cache and i else image, mask, max_new_tokens=NEW, **opts)   # None: the cached image block
+                rec.keep.append(out)
+                if prefix_cache:
+                    ids = torch.cat([ids, out[:, :-1], torch.tensor([[7, 9]])], 1)
+        return m
+    return fn
+
+
+SAMPLING = dict(do_sample=True, temperature=0.8, top_k=20, top_p=0.9)
+ARMS = ("greedy", "eos", "sampler-torch", "sampler-device", "penalty", "return-logits", "left-pad", "kv-fp8", "weights-fp8", "weights-int8",
+        "adapters-merged", "adapters-live", "constraint", "prefix-cache", "beam", "beam-eos", "beam-kv-fp8")
+R8 = dict(lora="r8")   # un-merged adapters
+
+
+def _generate_cases(c):
+    for B in (1, 2, 17):   # 1, 2: the session (B >= 2: re-tiled bf16 weights); 17: the GEMM step
+        c[f"generate/greedy/B{B}"] = generate_case(B)
+        c[f"generate/sampler-device/B{B}"] = generate_case(B, sampler="device", seed=7, **SAMPLING)
+        c[f"generate/constraint/B{B}"] = generate_case(B, constraint=True, return_choices=True)
+    for B in (2, 17):
+        c[f"generate/eos/B{B}"] = generate_case(B, eos_token_id=2)
+        c[f"generate/sampler-torch/B{B}"] = generate_case(B, seed=3, sampler="torch", **SAMPLING)
+        c[f"generate/penalty/B{B}"] = generate_case(B, repetition_penalty=1.3)
+        c[f"generate/return-logits/B{B}"] = generate_case(B, return_logits=True)
+        c[f"generate/weights-int8/B{B}"] = generate_case(B, base="int8", weights="int8")
+        c[f"generate/adapters-live/B{B}"] = generate_case(B, adapters="live", **R8)
+    c["generate/sampler-device-penalty/B2"] = generate_case(2, sampler="device", seed=7, repetition_penalty=1.3, **SAMPLING)
+    c["generate/left-pad/B2"] = generate_case(2, pad=True)
+    c["generate/kv-fp8/B2"] = generate_case(2, kv_cache="fp8")
+    c["generate/weights-fp8/B2"] = generate_case(2, weights="fp8")
+    c["generate/adapters-merged/B2"] = generate_case(2, adapters="merged", **R8)
+    c["generate/adapters-live/B2/weights-int8"] = generate_case(2, adapters="live", base="int8", weights="int8", **R8)
+    c["generate/prefix-cache/bf16"] = generate_case(1, calls=2, prefix_cache="bf16")
+    c["generate/prefix-cache/fp8"] = generate_case(1, calls=2, prefix_cache="fp8")
+    c["generate/streamer-criteria/B2"] = generate_case(2, streamer=_Streamer(), stopping_criteria=[lambda ids, lg: ids.shape[1] >= 4])
+    c["generate/no-graph/B2"] = generate_case(2, use_graph=False)
+    # keywords that generate() swallows: neither changes what is launched (the second equals generate/adapters-merged/B2)
+    c["generate/greedy/B2/return-sequences-none"] = generate_case(2, num_return_sequences=None)
+    c["generate/adapters-merged/B2/stray-live-lora"] = generate_case(2, adapters="merged", live_lora=True, **R8)
+    c["generate/beam/B2"] = generate_case(2, num_beams=2, return_beam_scores=True)
+    c["generate/beam-eos/B2"] = generate_case(2, num_beams=2, eos_token_id=2, repetition_penalty=1.3, length_penalty=0.5)
+    c["generate/beam-kv-fp8/B2"] = generate_case(2, num_beams=2, kv_cache="fp8", heads=16, dim=2048)   # 16 scale bytes of a position per chunk
+    c["generate/beam/B2/left-pad/adapters-live"] = generate_case(2, num_beams=2, pad=True, adapters="live", **R8)
+    # every rejection of a whole call, in the order they are made: (exception type, message, recorder calls made before it)
+    rej = dict(adapters=dict(adapters="fused"), **{"adapters-none": dict(adapters=None), "adapters-none/unmerged-adapters": dict(adapters=None, **R8)}, constraint=dict(constraint=True, do_sample=True), **{
+        "return-choices": dict(return_choices=True), "prefix-cache-batch": dict(prefix_cache="bf16"),
+        "prefix-cache-kv": dict(B=1, prefix_cache="bf16", kv_cache="fp8"), "kv-cache": dict(kv_cache="int8"),
+        "kv-fp8-17-rows": dict(B=17, kv_cache="fp8"), "kv-fp8-beam-heads": dict(num_beams=2, kv_cache="fp8"), "int8-without-base": dict(weights="int8"),
+        "sampler": dict(sampler="host"), "sampler/unmerged-adapters": dict(sampler="host", **R8), "beam-count": dict(num_beams=0),
+        "beam-sample": dict(num_beams=2, do_sample=True), "beam-streamer": dict(num_beams=2, streamer=_Streamer()),
+        "beam-criteria": dict(num_beams=2, stopping_criteria=[]), "beam-sequences": dict(num_beams=2, num_return_sequences=2),
+        "beam-early": dict(num_beams=2, early_stopping="never"), "beam-rows": dict(B=9, num_beams=2), "beam-width": dict(B=1, num_beams=9),
+        "beam-rows/unmerged-adapters": dict(B=9, num_beams=2, **R8), "4bit-merged": dict(base="4bit", weights="4bit", **R8),
+        "int8-merged": dict(base="int8", weights="int8", **R8), "unknown-weights": dict(weights="fp4")})
+    for name, kw in rej.items():
+        c[f"reject/generate/{name}"] = generate_case(**kw)
+
+
 def _cases():
     c = {}
     for w in WEIGHTS:
@@ -369,6 +503,7 @@ def _cases():
     c["reject/lora-over-768-rows/int8"] = session_case("int8", 2, "bf16", 32, lora=dict(r=264, alpha=16, targets=("q", "k", "v", "o")))
     c["reject/lora-lds"] = session_case("bf16", 16, "bf16", 32, lora=dict(r=8, alpha=16, targets=("down",)), layers=1, empty=True, **LDS_SHAPE)
     c["reject/generate-int8-without-base"] = generate_reject_case("int8")
+    _generate_cases(c)
     return c
 
 

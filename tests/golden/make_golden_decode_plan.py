@@ -4,7 +4,9 @@ message and the number of wrapper calls made before it.  No GPU - the wrappers a
 count of `lora_down` is asked from it.
 
 The file pins the host side of decoding across refactors: it is written from the commit BEFORE such a change and must come out byte for
-byte the same after it.  Regenerate it only with a change that is meant to alter what is launched.
+byte the same after it.  Regenerate it only with a change that is meant to alter what is launched.  (The `generate/` entries were recorded
+before the token loops became one; four `reject/generate/` counts - `sampler/unmerged-adapters`, `beam-rows`, `beam-width`,
+`beam-rows/unmerged-adapters` - were 4, 1, 1 and 5 then and are 0 since those checks moved in front of every launch.)
 
     python tests/golden/make_golden_decode_plan.py"""
 import json

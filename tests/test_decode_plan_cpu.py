@@ -33,6 +33,22 @@ def test_the_table_covers_every_format_boundary_and_rejection(golden):
     assert all("error" not in v for k, v in golden.items() if k.startswith("session/"))
 
 
+def test_the_table_holds_a_whole_generate_call_for_every_arm(golden):
+    whole = {k: v for k, v in golden.items() if k.startswith("generate/")}
+    assert whole and all("error" not in v for v in whole.values())
+    for arm in dp.ARMS:
+        assert any(k.startswith(f"generate/{arm}/") for k in whole), arm
+    for arm in ("greedy", "sampler-device", "constraint"):   # the session at batch 1 and 2, the GEMM step at batch 17
+        assert {f"generate/{arm}/B{B}" for B in (1, 2, 17)} <= set(whole)
+    assert all("HipGraph.launch" in whole[f"generate/greedy/B{B}"]["calls"] for B in (1, 2)) and "HipGraph.launch" not in whole["generate/greedy/B17"]["calls"]
+    rejected = {k[len("reject/generate/"):] for k in golden if k.startswith("reject/generate/")}
+    assert golden["generate/adapters-merged/B2/stray-live-lora"] == golden["generate/adapters-merged/B2"]
+    assert {"adapters", "adapters-none", "adapters-none/unmerged-adapters", "constraint", "prefix-cache-batch", "kv-cache", "int8-without-base", "sampler", "sampler/unmerged-adapters", "beam-count", "beam-sample",
+            "beam-streamer", "beam-criteria", "beam-sequences", "beam-early", "beam-rows", "4bit-merged", "int8-merged"} <= rejected
+    # a rejected call has made no wrapper call - but for `weights` outside the table, which the session itself rejects, behind the prefill
+    assert all(golden["reject/generate/" + k]["error"][2] == 0 for k in rejected - {"unknown-weights"})
+
+
 def test_every_public_wrapper_is_a_recorder():
     import lhrs_bot_amd.kernels as hk
     real = {n: getattr(hk, n) for n in dp.PUBLIC}
